@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's metric on the MI355X: Mpix/s through the fused curve-apply at
 1500x1000, batch 32 per GPU, plus PSNR delta vs the reference arithmetic (the oracle).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N=1 runs in this process.  N>1 under torch.distributed.run (RANK/WORLD_SIZE set: how the driver starts it) is one
 rank per GPU; N>1 started plainly launches `python -m torch.distributed.run --nproc-per-node N bench.py ...`
@@ -16,6 +16,11 @@ Rank 0 prints ONE compact JSON line on stdout (make_line: the contract's keys, `
 scalars and the literal-protocol figure; <= 4 KB, strict JSON -- tests/test_host_logic.py holds it to that).  Everything
 else (the other workloads' rows, the end-to-end and train-step records, the full accuracy block, board power) goes to
 bench_detail.json (beside this file and under gpurun_out/) and to stderr, never stdout.
+
+--dump-outputs DIR: after the timed steps, what the headline workload's last timed step returned is written as
+DIR/<name>.npy (host_outputs: float32, float64 where the kernel returns float64 or int64; < 64 MB in all, larger
+arrays as a fixed stratified sample).  The inputs are seeded, so two builds run with the same arguments can be compared
+array for array.  With N > 1, rank 0's shard.
 """
 import argparse
 import json
@@ -135,7 +140,7 @@ def make_step(name, ops, masks, sets=None):
             h, wd = w["hw"]
             dev = sets[0][0].device
             crops = [(s[0][:n, :, :h, :wd].contiguous(), s[1][:n], s[2][:n], s[3][:n]) for s in sets]
-            gout = torch.rand(n, 3, h, wd, device=dev)
+            gout = torch.rand(n, 3, h, wd, generator=torch.Generator().manual_seed(11)).to(dev)  # seeded: same every run
             m = torch.ones(n, 1, h, wd, dtype=torch.bool, device=dev)
             turn = [0]
 
@@ -206,9 +211,10 @@ def make_step(name, ops, masks, sets=None):
     raise ValueError(name)
 
 
-def timed_run(step, sets, steps, warmup, dist, device):
+def timed_run(step, sets, steps, warmup, dist, device, last=None):
     """W untimed warm-up steps, then EXACTLY K steps between barrier+synchronize brackets.
-    Returns (wall seconds max over ranks, mean device ms per step from events on the launch stream)."""
+    Returns (wall seconds max over ranks, mean device ms per step from events on the launch stream).
+    last: a list, if given, receives what the last timed step returned."""
     # Clock settle: after an idle gap the MI355X takes ~30 ms of continuous work to reach its steady clock
     # (profiles/r01/sustained_windows.log: the first ~100 launches of the arithmetic-heavy kernels run 15-25 %
     # slow).  These launches are untimed and come ON TOP of the W warm-up steps the contract asks for.
@@ -224,8 +230,13 @@ def timed_run(step, sets, steps, warmup, dist, device):
     ev1 = torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()  # torch's current stream == the stream the kernels are enqueued on (ops._stream)
-    for i in range(steps):
-        step(sets[i % len(sets)])
+    if last is None:
+        for i in range(steps):
+            step(sets[i % len(sets)])
+    else:  # nothing held across steps (the allocator sees what it sees without --dump-outputs) but the last step's result
+        for i in range(steps - 1):
+            step(sets[i % len(sets)])
+        last.append(step(sets[(steps - 1) % len(sets)]))
     ev1.record()
     torch.cuda.synchronize(device)
     if dist is not None:
@@ -240,6 +251,55 @@ def timed_run(step, sets, steps, warmup, dist, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, dev_ms, dev_min = float(t[0]), float(t[1]), -float(t[2])
     return wall, dev_ms, dev_min
+
+
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: array data in all, headers included well under 64 MB
+
+
+def _named_tensors(result, name="output"):
+    """The tensors a step returned, in return order: output, or output_0, output_1, ... (nested: output_2_0, ...)."""
+    if isinstance(result, torch.Tensor):
+        return [(name, result)]
+    if isinstance(result, (tuple, list)):
+        return [p for i, r in enumerate(result) for p in _named_tensors(r, f"{name}_{i}")]
+    if isinstance(result, (int, float)):
+        return [(name, torch.tensor(float(result), dtype=torch.float64))]
+    return []
+
+
+def host_outputs(result, budget=DUMP_BYTES):
+    """{name: (numpy array, full shape, sampled?)} of what one step returned, on the host: float64 where the tensor is
+    float64 or int64, float32 otherwise.  The smallest arrays are taken whole first; an array larger than its share of
+    what is left of `budget` becomes a fixed sample of its flattened elements: one per equal stratum, at an offset drawn
+    from a generator seeded by the array's position -- the same elements every run for the same shapes."""
+    items = [(n, t.detach()) for n, t in _named_tensors(result)]
+    dts = [torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32 for _, t in items]
+    order = sorted(range(len(items)), key=lambda i: items[i][1].numel() * dts[i].itemsize)
+    out, left = {}, budget
+    for j, i in enumerate(order):
+        name, t = items[i]
+        n = t.numel()
+        keep = min(n, max(1, left // (len(order) - j) // dts[i].itemsize))
+        flat = t.reshape(-1)
+        if keep < n:
+            g = torch.Generator().manual_seed(i)
+            base = torch.arange(keep, dtype=torch.int64) * n // keep
+            width = torch.arange(1, keep + 1, dtype=torch.int64) * n // keep - base
+            idx = base + (torch.rand(keep, generator=g, dtype=torch.float64) * width).long()
+            flat = flat.index_select(0, idx.to(flat.device))
+        a = flat.to(dts[i]).cpu().numpy()
+        out[name] = (a if keep < n else a.reshape(tuple(t.shape)), tuple(t.shape), keep < n)
+        left -= a.nbytes
+    return {n: out[n] for n, _ in items}  # in return order
+
+
+def write_outputs(directory, outputs):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, (a, shape, sampled) in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+        sys.stderr.write(f"bench.py: {directory}/{name}.npy {a.dtype} {list(a.shape)}"
+                         + (f" (fixed sample of {list(shape)})" if sampled else "") + "\n")
 
 
 class BoardPower:
@@ -675,6 +735,8 @@ def main():
     ap.add_argument("--workload", default="layer", choices=sorted(WORKLOADS))
     ap.add_argument("--no-extras", action="store_true", help="skip other_workloads / cpu_baseline / accuracy")
     ap.add_argument("--full", action="store_true", help="N > 1: measure the whole workload table, as N = 1 does")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline workload's last timed step returned "
+                    "to DIR/<name>.npy (float32/float64, < 64 MB in all; rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -724,14 +786,20 @@ def main():
     masks = {"disk": disk_mask(B, H_IMG, W_IMG, device),
              "ones": torch.ones(B, 1, H_IMG, W_IMG, dtype=torch.bool, device=device), None: None}
 
-    def measure(name, steps, warmup, cold=False):
+    dumped = {}
+
+    def measure(name, steps, warmup, cold=False, dump=False):
         w = WORKLOADS[name]
         bpp = w["bpp"]
         step = make_step(name, ops, masks, sets)
         npx_rank = workload_pixels(name, B)
         cold_us = cold_first_launch_us(step, sets, device) if cold else None
         cold_ms = cold_start_run(step, sets, steps, warmup, device) if cold and not args.no_extras else None
-        wall, dev_ms, dev_ms_min = timed_run(step, sets, steps, warmup, dist, device)
+        last = [] if dump else None
+        wall, dev_ms, dev_ms_min = timed_run(step, sets, steps, warmup, dist, device, last=last)
+        if dump:  # to the host now: nothing after the timed region may touch what the step returned
+            dumped.update(host_outputs(last[0]))
+            del last[:]
         power = None
         if cold and rank == 0 and not args.no_extras:
             # the hwmon power reading is a slow average (the ~0.3 s timed region is too short for it): the same step
@@ -782,7 +850,9 @@ def main():
             res["power"] = power
         return res
 
-    main_res = measure(args.workload, args.steps, args.warmup, cold=True)
+    main_res = measure(args.workload, args.steps, args.warmup, cold=True, dump=args.dump_outputs is not None and rank == 0)
+    if dumped:
+        write_outputs(args.dump_outputs, dumped)
     # N = 1: the whole table.  N > 1 (the scaling run): the headline, the two kernels north_star's targets name and the
     # data-parallel train step -- the time goes to the scaling number; --full restores the table
     names = [n for n in WORKLOADS if n != args.workload]

@@ -10,11 +10,11 @@ nothing under curl_amd/ does, and the product fails loudly without its HIP
 library instead of falling back to this code.
 
 Parity pin: tests/test_oracle_vs_reference.py compares every function here
-bit-for-bit with the reference's own modules imported from /root/reference
-(possible only in the build container), and tests/golden/*.npz holds outputs
-of the reference itself (generator: tests/golden/make_golden.py) that this
-file and the HIP path are both checked against wherever the reference cannot
-travel.
+bit-for-bit with the reference's own modules' outputs on the same inputs
+(stored in tests/golden/vs_reference.npz by make_golden_vs_reference.py), and
+tests/golden/*.npz holds further outputs of the reference itself (generator:
+tests/golden/make_golden.py) that this file and the HIP path are both checked
+against.
 
 Semantics where the reference is broken as written:
   * adjust_rgb/adjust_lab/adjust_hsv seed the regulariser with zeros(B)

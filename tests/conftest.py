@@ -10,7 +10,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = os.environ.get("CURL_REFERENCE", "/root/reference")
 
 
 def pytest_configure(config):
@@ -32,22 +31,6 @@ def golden():
             pytest.skip("tests/golden/real8.npz not present (tests/golden/README.md)")
         return np.load(path)
     return load
-
-
-@pytest.fixture(scope="session")
-def reference_modules():
-    """The reference's own curves/colors/transpose/metric modules -- build container only."""
-    if not os.path.isfile(os.path.join(REFERENCE, "curves.py")):
-        pytest.skip("reference tree not present (it never travels to the GPU box)")
-    sys.path.insert(0, REFERENCE)
-    try:
-        import colors
-        import curves
-        import metric
-        import transpose
-    finally:
-        sys.path.remove(REFERENCE)
-    return {"curves": curves, "colors": colors, "transpose": transpose, "metric": metric}
 
 
 HIP_CLANG = "/opt/rocm/lib/llvm/bin/clang++"

@@ -142,16 +142,11 @@ def test_reference_trispace_checkpoint_loads_strict(spatial, tmp_path):
         assert torch.equal(loaded.backbone.conv_stem.weight, conv["backbone.conv_stem.weight"])
 
 
-def test_non_backbone_keys_equal_the_reference_class():
+def test_non_backbone_keys_equal_the_reference_class(golden):
     """The reference's TriSpaceRegNet cannot be imported (timm, torchvision); its non-backbone state is what its
-    constructor registers (model.py:451-484): read the registrations from the source text and compare the names."""
-    path = "/root/reference/model.py"
-    if not os.path.isfile(path):
-        pytest.skip("reference tree not present")
-    src = open(path).read()
-    body = src[src.index("class TriSpaceRegNet"):]
-    body = body[:body.index("def cat_coords")]
-    attrs = set(re.findall(r"self\.(\w+)\s*=\s*(?:torch\.nn\.Parameter|nn\.Parameter|colors\.\w+\(|polylayer|timm\.)", body))
+    constructor registers (model.py:451-484): the registrations read from its source text (stored in
+    tests/golden/vs_reference.npz by make_golden_vs_reference.py), compared by name."""
+    attrs = {str(a) for a in golden("vs_reference")["trispace_attrs"]}
     assert {"x", "y", "rgb2lab", "lab2rgb", "rgb2hsv", "hsv2rgb", "polylayer", "backbone"} <= attrs
     mine = {k.split(".")[0] for k in model.TriSpaceRegNet(spatial=True).state_dict()}
     assert mine == {"x", "y", "rgb2lab", "lab2rgb", "rgb2hsv", "polylayer", "backbone"}  # hsv2rgb holds no tensor

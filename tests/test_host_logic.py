@@ -86,14 +86,18 @@ def test_state_dict_keys_match_reference():
     assert not any(p.requires_grad for p in layer.parameters())
 
 
-def test_colour_constants_match_reference_modules(reference_modules):
-    ref = reference_modules["colors"]
-    for mine, theirs in ((colors.RGB2LAB(), ref.RGB2LAB()), (colors.LAB2RGB(), ref.LAB2RGB()),
-                         (colors.RGB2HSV(), ref.RGB2HSV())):
-        a, b = mine.state_dict(), theirs.state_dict()
-        assert a.keys() == b.keys()
+COLOUR_MODULES = ("RGB2LAB", "LAB2RGB", "RGB2HSV")
+
+
+def test_colour_constants_match_reference_modules(golden):
+    """The reference's converter modules' state (stored in tests/golden/vs_reference.npz by make_golden_vs_reference.py)."""
+    ref = golden("vs_reference")
+    for name in COLOUR_MODULES:
+        a = getattr(colors, name)().state_dict()
+        assert set(a) == {str(k) for k in ref[f"colour_{name}_keys"]}, name
         for k in a:
-            assert torch.equal(a[k], b[k]), k
+            b = ref[f"colour_{name}_{k}"]
+            assert a[k].numpy().dtype == b.dtype and torch.equal(a[k], torch.from_numpy(b)), k
 
 
 def test_gcurlnet_structure_and_split():
@@ -130,24 +134,22 @@ def test_image_shard_is_a_partition():
         shard.image_shard(4, 2, 2)
 
 
-def test_convert_state_dict_matches_reference(reference_modules):
-    import importlib
-    import sys
-    from conftest import REFERENCE
-    from curl_amd.convert_state import convert_state_dict
-    sys.path.insert(0, REFERENCE)
-    try:
-        ref = importlib.import_module("convert_state")
-    finally:
-        sys.path.remove(REFERENCE)
+def convert_state_input():
     g = torch.Generator().manual_seed(0)
-    sd = {"module.rgb2lab.rgb_to_xyz": torch.rand(3, 3, generator=g), "module.lab2rgb.lab_to_fxfyfz": torch.rand(3, 3, generator=g),
-          "lab2rgb.xyz_to_rgb": torch.rand(1, 1, 3, 3, generator=g), "module.backbone.classifier.weight": torch.rand(4, 5, generator=g),
-          "rgb2hsv.comparison_zero": torch.tensor(0.0)}
-    a, b = convert_state_dict(sd), ref.convert_state_dict(sd)
-    assert list(a) == list(b)
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
+    return {"module.rgb2lab.rgb_to_xyz": torch.rand(3, 3, generator=g), "module.lab2rgb.lab_to_fxfyfz": torch.rand(3, 3, generator=g),
+            "lab2rgb.xyz_to_rgb": torch.rand(1, 1, 3, 3, generator=g), "module.backbone.classifier.weight": torch.rand(4, 5, generator=g),
+            "rgb2hsv.comparison_zero": torch.tensor(0.0)}
+
+
+def test_convert_state_dict_matches_reference(golden):
+    """The reference's convert_state_dict on the same state dict (stored in tests/golden/vs_reference.npz)."""
+    from curl_amd.convert_state import convert_state_dict
+    ref = golden("vs_reference")
+    a = convert_state_dict(convert_state_input())
+    assert list(a) == [str(k) for k in ref["convert_state_keys"]]
+    for i, k in enumerate(a):
+        b = ref[f"convert_state_{i}"]
+        assert a[k].numpy().dtype == b.dtype and torch.equal(a[k], torch.from_numpy(b)), k
 
 
 def test_reference_style_checkpoint_loads_into_curllayer():
@@ -409,3 +411,32 @@ def test_scaling_run_measures_the_targets_only():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     assert set(bench.SCALING_RUN_WORKLOADS) == {"lab_stage", "rgb_only"} and set(bench.SCALING_RUN_WORKLOADS) < set(bench.WORKLOADS)
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """--dump-outputs: small arrays whole in their shape, a large one as the same stratified sample every run, float32
+    (float64 for float64 / int64 tensors), the data within the byte budget; the files are DIR/<name>.npy."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    g = torch.Generator().manual_seed(3)
+    img, reg = torch.rand(2, 3, 40, 50, generator=g), torch.rand(2, generator=g)
+    extra = [torch.arange(5), torch.ones(2, 2, dtype=torch.uint8), 1.5]
+    budget = 4000
+    a = bench.host_outputs((img, reg, extra), budget=budget)
+    b = bench.host_outputs((img.clone(), reg.clone(), extra), budget=budget)
+    assert list(a) == ["output_0", "output_1", "output_2_0", "output_2_1", "output_2_2"]
+    assert sum(v[0].nbytes for v in a.values()) <= budget
+    arr, shape, sampled = a["output_0"]
+    assert sampled and shape == (2, 3, 40, 50) and arr.dtype == np.float32 and 0 < arr.size < img.numel()
+    assert np.array_equal(arr, b["output_0"][0]) and np.isin(arr, img.numpy()).all()
+    idx = [int(np.flatnonzero(img.numpy().ravel() == v)[0]) for v in arr[:50]]
+    assert idx == sorted(idx) and len(set(idx)) == len(idx)  # one element per stratum, in order
+    assert not a["output_1"][2] and np.array_equal(a["output_1"][0], reg.numpy())
+    assert a["output_2_0"][0].dtype == np.float64 and a["output_2_1"][0].shape == (2, 2)
+    assert a["output_2_2"][0].dtype == np.float64 and float(a["output_2_2"][0]) == 1.5
+    assert bench.host_outputs((img, reg))["output_0"][0].shape == img.shape  # within the default budget: whole
+    bench.write_outputs(str(tmp_path / "dump"), a)
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted(k + ".npy" for k in a)
+    assert np.array_equal(np.load(tmp_path / "dump" / "output_0.npy"), arr)
