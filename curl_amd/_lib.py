@@ -54,6 +54,18 @@ SIGNATURES = {
     "curl_layer_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "curl_layer_bwd_f32": (_i, [_c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                 _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _i, _i, _u, _c_f]),
+    # backward of the stand-alone curve ops, converters and fused stages
+    "curl_adjust_rgb_bwd_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u, _c_f]),
+    "curl_adjust_lab_bwd_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u, _c_f]),
+    "curl_adjust_hsv_bwd_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u, _c_f]),
+    "curl_rgb2lab_bwd_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _u, _c_f]),
+    "curl_lab2rgb_bwd_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _u, _c_f]),
+    "curl_rgb2hsv_bwd_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _u, _c_f]),
+    "curl_hsv2rgb_bwd_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _u, _c_f]),
+    "curl_lab_stage_bwd_f32": (_i, [_c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u,
+                                    _c_f]),
+    "curl_hsv_stage_bwd_f32": (_i, [_c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u,
+                                    _c_f]),
     "curl_trispace_fwd_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),
     "curl_trispace_fwd_slab_f32": (_i, [_c_f, _c_f, _c_f, _i, _i, _i, _i, _i, _i, _u, _c_f]),
     "curl_trispace_fwd_u8hwc": (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),

@@ -474,6 +474,57 @@ CURL_HD Px curl_layer_bwd(Px in, float m, const LayerCoef& k, Px gout, float* P,
   return Px{g.c0 + g_pre.c0, g.c1 + g_pre.c1, g.c2 + g_pre.c2};
 }
 
+// ---------------------------------------------------------------- the stand-alone curve ops and stages, one pixel each
+// (the backward of curl_adjust_*_f32, curl_lab_stage_f32 and curl_hsv_stage_f32: stage_bwd.inc, and the host twin).
+// P, Q [3] (adjust3, the Lab stage) or [4] (adjust_hsv, the HSV stage): += per curve.  Returns d loss / d in.
+// A stand-alone adjust_hsv meets whatever the caller hands it: the general (UNIT = false) forms, input clamps gated.
+CURL_HD Px adjust3_bwd(Px in, const Affine* k, Px g, float* P, float* Q) {  // curves.py:90-133 / 136-180
+  Adjust3T t;
+  adjust3_t(in, k, t);
+  return adjust3_pull(t, g, P, Q);
+}
+CURL_HD Px adjust_hsv_bwd(Px in, const Affine* k, Px g, float* P, float* Q) {  // curves.py:41-87
+  AdjustHsvT t;
+  adjust_hsv4_t<false>(in, k, t);
+  return adjust_hsv4_pull<false>(t, k, g, P, Q);
+}
+// model.py:151-157: rgb2lab -> adjust_lab -> *mask -> lab2rgb.  BINARY: m is exactly 0 or 1 -- the incoming gradient times
+// m is 0 where the pixel is masked out and every product on the way back is an exact 0 (curl_layer_bwd); where m == 1 the
+// intermediate multiply is the identity.  NEED_GIN = false: the chain stops at the curves' sums (P, Q the same bits).
+template <bool BINARY, bool NEED_GIN = true>
+CURL_HD Px lab_stage_bwd(Px in, float m, const Affine* k, Px gout, float* P, float* Q) {
+  Rgb2LabT t_lab;
+  Adjust3T t_al;
+  Lab2RgbT t_rgb;
+  Px x = adjust3_t(rgb2lab_t(in, t_lab), k, t_al);
+  if (!BINARY) x = Px{x.c0 * m, x.c1 * m, x.c2 * m};  // model.py:154
+  lab2rgb_t(x, t_rgb);
+  Px g = BINARY ? Px{gout.c0 * m, gout.c1 * m, gout.c2 * m} : gout;
+  g = lab2rgb_pull(t_rgb, g);
+  if (!BINARY) g = Px{g.c0 * m, g.c1 * m, g.c2 * m};
+  g = adjust3_pull(t_al, g, P, Q);
+  if constexpr (!NEED_GIN) return g;
+  return rgb2lab_pull(t_lab, g);
+}
+// model.py:163-169: rgb2hsv -> adjust_hsv -> *mask -> hsv2rgb, the residual curl_hsv_stage_f32 returns.  adjust_hsv's s and v
+// arrive out of rgb2hsv's output clamp (UNIT); hsv2rgb's input is in [0,1] only for a binary mask (a float mask can be
+// anything: the general form there, as the forward's hsv2rgb<BINARY>).
+template <bool BINARY, bool NEED_GIN = true>
+CURL_HD Px hsv_stage_bwd(Px in, float m, const Affine* k, Px gout, float* P, float* Q) {
+  Rgb2HsvT t_hsv;
+  AdjustHsvT t_ah;
+  Hsv2RgbT t_res;
+  Px x = adjust_hsv4_t<true>(rgb2hsv_t(in, t_hsv), k, t_ah);
+  if (!BINARY) x = Px{x.c0 * m, x.c1 * m, x.c2 * m};  // model.py:166
+  hsv2rgb_t<BINARY>(x, t_res);
+  Px g = BINARY ? Px{gout.c0 * m, gout.c1 * m, gout.c2 * m} : gout;  // (binary: hsv2rgb(hsv) * m, hsv_stage_n)
+  g = hsv2rgb_pull<BINARY>(t_res, g);
+  if (!BINARY) g = Px{g.c0 * m, g.c1 * m, g.c2 * m};
+  g = adjust_hsv4_pull<true>(t_ah, k, g, P, Q);
+  if constexpr (!NEED_GIN) return g;
+  return rgb2hsv_pull(t_hsv, g);
+}
+
 // ---- per image: (P, Q) of one curve + d loss / d reg  ->  gradient of that curve's RAW knots (pre-exp).
 // C = exp(raw) (already computed); scale = C0 + sum_{j<=K-3} slope_j (S x - j); reg = sum_j (slope_{j+1}-slope_j)^2.
 // Everything in float64: K is tiny and this runs once per curve per image.

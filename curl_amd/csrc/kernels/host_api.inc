@@ -523,12 +523,101 @@ static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, con
   return hipGetLastError();
 }
 
+// The backward of one knot segment of 3 (adjust_rgb / adjust_lab, the Lab stage) or 4 curves (adjust_hsv, the HSV stage):
+// arguments checked before any HIP call, the knot prep unless CURL_F_WS_READY, stage_bwd_kernel, stage_knots_bwd_kernel.
+template <int OP>
+static int stage_bwd_common(const float* img, const void* mask, int mask_kind, const float* raw, const float* grad_out,
+                            const float* grad_reg, float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, int B, int H, int W, int K, unsigned flags,
+                            curl_stream_t stream, const char* name) {
+  constexpr int NC = StageCurves<OP>::kN;
+  g_err[0] = 0;
+  if (int rc = check_img(img, grad_out, B, H, W)) return rc;
+  if (!raw) return fail(CURL_E_NULL, "raw knot pointer is NULL");
+  if (!grad_raw) return fail(CURL_E_NULL, "grad_raw is NULL");
+  if (int rc = check_mask(mask, mask_kind)) return rc;
+  if (int rc = check_K(K, true)) return rc;
+  if (flags & CURL_F_PWL) return fail(CURL_E_FLAGS, "CURL_F_PWL has no backward");
+  if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;
+  const int n_knots = KP_TOTAL(K, NC);
+  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
+  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_layer_bwd_scratch_bytes(B, H, W))
+    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  const unsigned stride = ws_stride(n_knots);
+  if (!(flags & CURL_F_WS_READY))
+    if (int rc = run_prep(raw, NC, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, nullptr, B, s)) return rc;
+  const size_t HW = (size_t)H * W;
+  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
+  StageBwdArgs a;
+  a.in = img;
+  a.gout = grad_out;
+  a.gin = grad_img;
+  a.mask = mask_kind ? mask : nullptr;
+  a.coef = ws;
+  a.partial = (float*)scratch;
+  a.coef_stride = stride;
+  a.n = (unsigned)(HW / (aligned ? 4 : 1));
+  a.blocks_per_image = (a.n + 255u) / 256u;
+  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
+  a.stamp = ws_stamp((unsigned)n_knots, stride);
+  if ((uint64_t)a.blocks_per_image * (uint64_t)B > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
+  const dim3 grid(a.blocks_per_image, (unsigned)B), block(256);
+#define LAUNCH_STAGE_BWD(V, M)                                                                     \
+  do {                                                                                             \
+    if (grad_img) hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, true>), grid, block, 0, s, a);    \
+    else hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, false>), grid, block, 0, s, a);            \
+  } while (0)
+  if constexpr (OP == STAGE_LAB || OP == STAGE_HSV) {
+    DISPATCH_VEC_MASK(LAUNCH_STAGE_BWD, aligned, mask_kind);
+  } else {
+    if (aligned) LAUNCH_STAGE_BWD(4, CURL_MASK_NONE);
+    else LAUNCH_STAGE_BWD(1, CURL_MASK_NONE);
+  }
+#undef LAUNCH_STAGE_BWD
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, name);
+  StageKnotsArgs kb;
+  kb.ws = ws;
+  kb.partial = (const float*)scratch;
+  kb.greg = grad_reg;
+  kb.graw = grad_raw;
+  kb.K = K;
+  kb.ws_stride = stride;
+  kb.blocks_per_image = a.blocks_per_image;
+  hipLaunchKernelGGL(stage_knots_bwd_kernel<NC>, dim3((unsigned)B), dim3(STAGE_KNOTS_THREADS), 0, s, kb);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "stage_knots_bwd_kernel");
+  return 0;
+}
+
+template <int CONV>
+static int convert_bwd_common(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                              curl_stream_t stream, const char* name) {
+  g_err[0] = 0;
+  if (int rc = check_img(in, grad_out, B, H, W)) return rc;
+  if (!grad_in) return fail(CURL_E_NULL, "grad_in is NULL");
+  if (int rc = check_flags(flags, 0)) return rc;
+  const size_t HW = (size_t)H * W;
+  const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, in, grad_out, grad_in);
+  ConvBwdArgs a{in, grad_out, grad_in, (unsigned)(HW / (aligned ? 4 : 1))};
+  const dim3 grid((a.n + 255u) / 256u, (unsigned)B), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (aligned) hipLaunchKernelGGL((convert_bwd_kernel<CONV, 4>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((convert_bwd_kernel<CONV, 1>), grid, block, 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, name);
+  return 0;
+}
+
 extern "C" {
 
 // 0.1.5: round 4 (CURL_F_TUNE_PREP: curves collapsed inside the streaming kernel for small launches; stamped workspace rows)
 // 0.1.6: same entry points; curl_layer_bwd_f32 with grad_img = NULL runs its own kernel; gradients at black pixels, at
 //        prediction == target (CURLLoss) and the PSNR of equal images under a float mask follow the reference (DESIGN.md 3e.8-9)
-int curl_version(void) { return 108; }
+// 0.1.9: backward entry points of the stand-alone curve ops, converters and fused stages (curl_*_bwd_f32)
+int curl_version(void) { return 109; }
 
 const char* curl_last_error(void) { return g_err; }
 
@@ -819,6 +908,58 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "knots_bwd_kernel");
   return 0;
+}
+
+int curl_adjust_rgb_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes, void* scratch,
+                            size_t scratch_bytes, int B, int H, int W, int K, unsigned flags, curl_stream_t stream) {
+  return stage_bwd_common<STAGE_ADJ3>(img, nullptr, CURL_MASK_NONE, raw, grad_out, grad_reg, grad_img, grad_raw, workspace,
+                                      workspace_bytes, scratch, scratch_bytes, B, H, W, K, flags & ~CURL_F_MASK_FIRST, stream,
+                                      "adjust_rgb_bwd");
+}
+int curl_adjust_lab_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes, void* scratch,
+                            size_t scratch_bytes, int B, int H, int W, int K, unsigned flags, curl_stream_t stream) {
+  return stage_bwd_common<STAGE_ADJ3>(img, nullptr, CURL_MASK_NONE, raw, grad_out, grad_reg, grad_img, grad_raw, workspace,
+                                      workspace_bytes, scratch, scratch_bytes, B, H, W, K, flags & ~CURL_F_MASK_FIRST, stream,
+                                      "adjust_lab_bwd");
+}
+int curl_adjust_hsv_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes, void* scratch,
+                            size_t scratch_bytes, int B, int H, int W, int K, unsigned flags, curl_stream_t stream) {
+  return stage_bwd_common<STAGE_AHSV>(img, nullptr, CURL_MASK_NONE, raw, grad_out, grad_reg, grad_img, grad_raw, workspace,
+                                      workspace_bytes, scratch, scratch_bytes, B, H, W, K, flags & ~CURL_F_MASK_FIRST, stream,
+                                      "adjust_hsv_bwd");
+}
+int curl_rgb2lab_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream) {
+  return convert_bwd_common<CONV_RGB2LAB>(in, grad_out, grad_in, B, H, W, flags, stream, "rgb2lab_bwd");
+}
+int curl_lab2rgb_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream) {
+  return convert_bwd_common<CONV_LAB2RGB>(in, grad_out, grad_in, B, H, W, flags, stream, "lab2rgb_bwd");
+}
+int curl_rgb2hsv_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream) {
+  return convert_bwd_common<CONV_RGB2HSV>(in, grad_out, grad_in, B, H, W, flags, stream, "rgb2hsv_bwd");
+}
+int curl_hsv2rgb_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream) {
+  return convert_bwd_common<CONV_HSV2RGB>(in, grad_out, grad_in, B, H, W, flags, stream, "hsv2rgb_bwd");
+}
+int curl_lab_stage_bwd_f32(const float* img, const void* mask, int mask_kind, const float* rawL, const float* grad_out,
+                           const float* grad_reg, float* grad_img, float* grad_rawL, void* workspace, size_t workspace_bytes,
+                           void* scratch, size_t scratch_bytes, int B, int H, int W, int Kl, unsigned flags,
+                           curl_stream_t stream) {
+  return stage_bwd_common<STAGE_LAB>(img, mask, mask_kind, rawL, grad_out, grad_reg, grad_img, grad_rawL, workspace,
+                                     workspace_bytes, scratch, scratch_bytes, B, H, W, Kl, flags, stream, "lab_stage_bwd");
+}
+int curl_hsv_stage_bwd_f32(const float* img, const void* mask, int mask_kind, const float* rawH, const float* grad_out,
+                           const float* grad_reg, float* grad_img, float* grad_rawH, void* workspace, size_t workspace_bytes,
+                           void* scratch, size_t scratch_bytes, int B, int H, int W, int Kh, unsigned flags,
+                           curl_stream_t stream) {
+  return stage_bwd_common<STAGE_HSV>(img, mask, mask_kind, rawH, grad_out, grad_reg, grad_img, grad_rawH, workspace,
+                                     workspace_bytes, scratch, scratch_bytes, B, H, W, Kh, flags, stream, "hsv_stage_bwd");
 }
 
 static int trispace_fwd_impl(const float* img, const float* coeffs, float* out, int B, int H, int W, int num_coeffs,

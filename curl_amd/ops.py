@@ -193,7 +193,10 @@ def _ptr(t):
 @_empty_ok(mask_arg=-1)
 def apply_curve(img, C, slope_sqr_diff, channel_in, channel_out, flags=F_EXACT_ORDER):
     """curves.apply_curve (curves.py:4-38).  C are the knots after exp, [B,K].
-    slope_sqr_diff [B] is updated in place (curves.py:24) and returned; None skips it."""
+    slope_sqr_diff [B] is updated in place (curves.py:24) and returned; None skips it.  Forward only."""
+    if _grad_wanted(img, C, slope_sqr_diff):
+        raise NotImplementedError("curl_amd: apply_curve has no backward; adjust_rgb / adjust_lab / adjust_hsv and the "
+                                  "stages are differentiable. Use torch.no_grad() here.")
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
@@ -210,7 +213,7 @@ def apply_curve(img, C, slope_sqr_diff, channel_in, channel_out, flags=F_EXACT_O
     return out, reg
 
 
-def _adjust(fn_name, ncurves, img, raw, flags):  # noqa: E302
+def _adjust(fn_name, ncurves, img, raw, flags, return_workspace=False):  # noqa: E302
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
@@ -221,28 +224,46 @@ def _adjust(fn_name, ncurves, img, raw, flags):  # noqa: E302
     rc = getattr(lib, fn_name)(img.data_ptr(), rawc.data_ptr(), out.data_ptr(), reg.data_ptr(), ws.data_ptr(), nbytes,
                                B, H, W, K, flags, _stream(img))
     _lib.check(rc, fn_name)
-    return out, reg
+    return (out, reg, ws) if return_workspace else (out, reg)
 
 
 @_one_device
 @_empty_ok(mask_arg=-1)
+def _adjust_rgb(img, R, flags=0, return_workspace=False):
+    return _adjust("curl_adjust_rgb_f32", 3, img, R, flags, return_workspace)
+
+
+@_one_device
+@_empty_ok(mask_arg=-1)
+def _adjust_lab(img, L, flags=0, return_workspace=False):
+    return _adjust("curl_adjust_lab_f32", 3, img, L, flags, return_workspace)
+
+
+@_one_device
+@_empty_ok(mask_arg=-1)
+def _adjust_hsv(img, S, flags=0, return_workspace=False):
+    return _adjust("curl_adjust_hsv_f32", 4, img, S, flags, return_workspace)
+
+
 def adjust_rgb(img, R, flags=0):
-    """curves.adjust_rgb (curves.py:90-133), regulariser seeded with zeros."""
-    return _adjust("curl_adjust_rgb_f32", 3, img, R, flags)
+    """curves.adjust_rgb (curves.py:90-133), regulariser seeded with zeros.  Differentiable (image and knots)."""
+    if _grad_wanted(img, R):
+        return _curve_op_grad("adjust_rgb", img, None, R, flags)
+    return _adjust_rgb(img, R, flags)
 
 
-@_one_device
-@_empty_ok(mask_arg=-1)
 def adjust_lab(img, L, flags=0):
-    """curves.adjust_lab (curves.py:136-180)."""
-    return _adjust("curl_adjust_lab_f32", 3, img, L, flags)
+    """curves.adjust_lab (curves.py:136-180).  Differentiable (image and knots)."""
+    if _grad_wanted(img, L):
+        return _curve_op_grad("adjust_lab", img, None, L, flags)
+    return _adjust_lab(img, L, flags)
 
 
-@_one_device
-@_empty_ok(mask_arg=-1)
 def adjust_hsv(img, S, flags=0):
-    """curves.adjust_hsv (curves.py:41-87)."""
-    return _adjust("curl_adjust_hsv_f32", 4, img, S, flags)
+    """curves.adjust_hsv (curves.py:41-87).  Differentiable (image and knots)."""
+    if _grad_wanted(img, S):
+        return _curve_op_grad("adjust_hsv", img, None, S, flags)
+    return _adjust_hsv(img, S, flags)
 
 
 # ------------------------------------------------------------------ colors.py
@@ -258,37 +279,68 @@ def _convert(fn_name, img, flags=0):
 
 @_one_device
 @_empty_ok()
-def rgb2lab(img, flags=0):
-    """colors.RGB2LAB.forward (colors.py:27-62)."""
+def _rgb2lab(img, flags=0):
     return _convert("curl_rgb2lab_f32", img, flags)
 
 
+def rgb2lab(img, flags=0):
+    """colors.RGB2LAB.forward (colors.py:27-62).  Differentiable."""
+    if _grad_wanted(img):
+        return _ConvertFn.apply("rgb2lab", img, flags)
+    return _rgb2lab(img, flags)
+
+
 @_one_device
 @_empty_ok()
-def lab2rgb(img, flags=0):
-    """colors.LAB2RGB.forward (colors.py:88-123)."""
+def _lab2rgb(img, flags=0):
     return _convert("curl_lab2rgb_f32", img, flags)
 
 
+def lab2rgb(img, flags=0):
+    """colors.LAB2RGB.forward (colors.py:88-123).  Differentiable."""
+    if _grad_wanted(img):
+        return _ConvertFn.apply("lab2rgb", img, flags)
+    return _lab2rgb(img, flags)
+
+
 @_one_device
 @_empty_ok()
-def rgb2hsv(img, flags=0):
-    """colors.RGB2HSV.forward (colors.py:195-242)."""
+def _rgb2hsv(img, flags=0):
     return _convert("curl_rgb2hsv_f32", img, flags)
 
 
+def rgb2hsv(img, flags=0):
+    """colors.RGB2HSV.forward (colors.py:195-242).  Differentiable."""
+    if _grad_wanted(img):
+        return _ConvertFn.apply("rgb2hsv", img, flags)
+    return _rgb2hsv(img, flags)
+
+
 @_one_device
 @_empty_ok()
-def hsv2rgb(img, flags=0):
-    """colors.HSV2RGB.forward (colors.py:131-177)."""
+def _hsv2rgb(img, flags=0):
     return _convert("curl_hsv2rgb_f32", img, flags)
 
 
+def hsv2rgb(img, flags=0):
+    """colors.HSV2RGB.forward (colors.py:131-177).  Differentiable."""
+    if _grad_wanted(img):
+        return _ConvertFn.apply("hsv2rgb", img, flags)
+    return _hsv2rgb(img, flags)
+
+
 # ------------------------------------------------------------------ model.py: fused stages
+def lab_stage(img, mask, L, flags=0, out=None):
+    """RGB -> Lab -> 3 curves -> *mask -> RGB in one pass (model.py:151-157). -> (rgb, reg_lab).
+    Differentiable (image and knots; no mask gradient) in the default affine form."""
+    if _grad_wanted(img, L):
+        return _curve_op_grad("lab_stage", img, mask, L, flags, out)
+    return _lab_stage(img, mask, L, flags=flags, out=out)
+
+
 @_one_device
 @_empty_ok(mask_arg=0)
-def lab_stage(img, mask, L, flags=0, out=None):
-    """RGB -> Lab -> 3 curves -> *mask -> RGB in one pass (model.py:151-157). -> (rgb, reg_lab)."""
+def _lab_stage(img, mask, L, flags=0, out=None, return_workspace=False):
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
@@ -300,13 +352,20 @@ def lab_stage(img, mask, L, flags=0, out=None):
     rc = lib.curl_lab_stage_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), out.data_ptr(), reg.data_ptr(),
                                 ws.data_ptr(), nbytes, B, H, W, Kl, flags, _stream(img))
     _lib.check(rc, "curl_lab_stage_f32")
-    return out, reg
+    return (out, reg, ws) if return_workspace else (out, reg)
+
+
+def hsv_stage(img, mask, H, flags=0, out=None):
+    """RGB -> HSV -> 4 curves -> *mask -> RGB in one pass (model.py:163-169): the layer's RGB residual. -> (rgb, reg_hsv).
+    Differentiable (image and knots; no mask gradient)."""
+    if _grad_wanted(img, H):
+        return _curve_op_grad("hsv_stage", img, mask, H, flags, out)
+    return _hsv_stage(img, mask, H, flags=flags, out=out)
 
 
 @_one_device
 @_empty_ok(mask_arg=0)
-def hsv_stage(img, mask, H, flags=0, out=None):
-    """RGB -> HSV -> 4 curves -> *mask -> RGB in one pass (model.py:163-169): the layer's RGB residual. -> (rgb, reg_hsv)."""
+def _hsv_stage(img, mask, H, flags=0, out=None, return_workspace=False):
     lib = _lib.load()
     img = _image(img)
     B, _, Hh, W = img.shape
@@ -318,7 +377,7 @@ def hsv_stage(img, mask, H, flags=0, out=None):
     rc = lib.curl_hsv_stage_f32(img.data_ptr(), _ptr(m), kind, Hc.data_ptr(), out.data_ptr(), reg.data_ptr(),
                                 ws.data_ptr(), nbytes, B, Hh, W, Kh, flags, _stream(img))
     _lib.check(rc, "curl_hsv_stage_f32")
-    return out, reg
+    return (out, reg, ws) if return_workspace else (out, reg)
 
 
 def curl_layer_forward(img, mask, L, R, H, flags=0, out=None, return_workspace=False):
@@ -458,6 +517,188 @@ def _curl_layer_backward_checked(img, mask, L, R, H, grad_out, grad_reg=None, ne
                                 bflags, _stream(img))
     _lib.check(rc, "curl_layer_bwd_f32")
     return g_img, gL, gR, gH
+
+
+# ------------------------------------------------------------------ backward of the stand-alone curve ops and stages
+def _grad_reg32(grad_reg, B):
+    if grad_reg is None:
+        return None
+    _need_device(grad_reg, "grad_reg")
+    grad_reg = grad_reg.to(torch.float32).contiguous()
+    if grad_reg.shape != (B,):
+        raise ValueError("grad_reg must be [B]")
+    return grad_reg
+
+
+# op -> (C entry point, curves, forward, takes a mask)
+_CURVE_BWD = {
+    "adjust_rgb": ("curl_adjust_rgb_bwd_f32", 3, "_adjust_rgb", False),
+    "adjust_lab": ("curl_adjust_lab_bwd_f32", 3, "_adjust_lab", False),
+    "adjust_hsv": ("curl_adjust_hsv_bwd_f32", 4, "_adjust_hsv", False),
+    "lab_stage": ("curl_lab_stage_bwd_f32", 3, "_lab_stage", True),
+    "hsv_stage": ("curl_hsv_stage_bwd_f32", 4, "_hsv_stage", True),
+}
+
+
+@_one_device
+def _curve_backward(op, img, mask, raw, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
+    """-> (grad_img or None, grad_raw): the backward of one stand-alone curve op or stage (_CURVE_BWD)."""
+    fn_name, ncurves, _, masked = _CURVE_BWD[op]
+    lib = _lib.load()
+    if isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0:
+        # an empty image owes only the regulariser's share: the same entry point on a 1x1 stand-in with a zero gradient
+        _need_device(img, "img")
+        B = img.shape[0]
+        g_img = torch.empty_like(img) if need_grad_img else None
+        if B == 0:
+            return g_img, torch.zeros(raw.shape, dtype=torch.float32, device=img.device)
+        z = img.new_zeros((B, 3, 1, 1))
+        _, g_raw = _curve_backward(op, z, None, raw, z, grad_reg, False, None, flags)
+        return g_img, g_raw
+    img = _image(img)
+    grad_out = _image(grad_out, "grad_out")
+    if grad_out.shape != img.shape:
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    B, _, Hh, W = img.shape
+    rawc, K = _knots(raw, "knots", ncurves, B)
+    grad_reg = _grad_reg32(grad_reg, B)
+    g_img = torch.empty_like(img) if need_grad_img else None
+    g_raw = torch.empty_like(rawc)
+    ws, nbytes = _workspace(B, rawc.shape[1], img.device)
+    bflags = flags & F_MASK_FIRST
+    if workspace is not None:
+        if workspace.device != img.device or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
+            raise ValueError(f"workspace is not the tensor ops.{op} filled for this batch")
+        ws, bflags = workspace, bflags | _lib.F_WS_READY
+    sbytes = lib.curl_layer_bwd_scratch_bytes(B, Hh, W)
+    scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
+    head = (img.data_ptr(),)
+    if masked:
+        m, kind = _mask(mask, img)
+        head = (img.data_ptr(), _ptr(m), kind)
+    rc = getattr(lib, fn_name)(*head, rawc.data_ptr(), grad_out.data_ptr(), _ptr(grad_reg), _ptr(g_img), g_raw.data_ptr(),
+                               ws.data_ptr(), nbytes, scratch.data_ptr(), sbytes, B, Hh, W, K, bflags, _stream(img))
+    _lib.check(rc, fn_name)
+    return g_img, g_raw
+
+
+def adjust_rgb_backward(img, R, grad_out, grad_reg=None, need_grad_img=True, workspace=None):
+    """Backward of adjust_rgb (torch autograd through curves.py:90-133). -> (grad_img or None, grad_R).
+    workspace: the one adjust_rgb filled for the SAME knots (CURL_F_WS_READY: no knot-prep launch)."""
+    return _curve_backward("adjust_rgb", img, None, R, grad_out, grad_reg, need_grad_img, workspace)
+
+
+def adjust_lab_backward(img, L, grad_out, grad_reg=None, need_grad_img=True, workspace=None):
+    """Backward of adjust_lab (curves.py:136-180). -> (grad_img or None, grad_L)."""
+    return _curve_backward("adjust_lab", img, None, L, grad_out, grad_reg, need_grad_img, workspace)
+
+
+def adjust_hsv_backward(img, S, grad_out, grad_reg=None, need_grad_img=True, workspace=None):
+    """Backward of adjust_hsv (curves.py:41-87). -> (grad_img or None, grad_S)."""
+    return _curve_backward("adjust_hsv", img, None, S, grad_out, grad_reg, need_grad_img, workspace)
+
+
+def lab_stage_backward(img, mask, L, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
+    """Backward of lab_stage (model.py:151-157). -> (grad_img or None, grad_L); no mask gradient.
+    flags: F_MASK_FIRST is honoured (bool / uint8 foreground masks), nothing else."""
+    return _curve_backward("lab_stage", img, mask, L, grad_out, grad_reg, need_grad_img, workspace, flags)
+
+
+def hsv_stage_backward(img, mask, H, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
+    """Backward of hsv_stage (model.py:163-169). -> (grad_img or None, grad_H); no mask gradient."""
+    return _curve_backward("hsv_stage", img, mask, H, grad_out, grad_reg, need_grad_img, workspace, flags)
+
+
+@_one_device
+def _convert_backward(name, img, grad_out):
+    if isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0:
+        _need_device(img, "img")
+        return torch.empty_like(img)
+    lib = _lib.load()
+    img = _image(img)
+    grad_out = _image(grad_out, "grad_out")
+    if grad_out.shape != img.shape:
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    g = torch.empty_like(img)
+    fn_name = f"curl_{name}_bwd_f32"
+    rc = getattr(lib, fn_name)(img.data_ptr(), grad_out.data_ptr(), g.data_ptr(), B, H, W, 0, _stream(img))
+    _lib.check(rc, fn_name)
+    return g
+
+
+def rgb2lab_backward(img, grad_out):
+    """Backward of rgb2lab (autograd through colors.py:27-62) at the input img. -> grad_img."""
+    return _convert_backward("rgb2lab", img, grad_out)
+
+
+def lab2rgb_backward(img, grad_out):
+    """Backward of lab2rgb (colors.py:88-123). -> grad_img."""
+    return _convert_backward("lab2rgb", img, grad_out)
+
+
+def rgb2hsv_backward(img, grad_out):
+    """Backward of rgb2hsv (colors.py:195-242). -> grad_img."""
+    return _convert_backward("rgb2hsv", img, grad_out)
+
+
+def hsv2rgb_backward(img, grad_out):
+    """Backward of hsv2rgb (colors.py:131-177). -> grad_img."""
+    return _convert_backward("hsv2rgb", img, grad_out)
+
+
+def _grad_wanted(*tensors):
+    """The test CURLLayer.forward uses: an autograd node only when grad mode is on and some tensor input requires grad."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+class _CurveOpFn(torch.autograd.Function):
+    """Autograd node of a stand-alone curve op or stage (_CURVE_BWD), as model._CurlLayerFn: the forward is the no-grad
+    call (the same launches, the same bits), its knot workspace rides along to the backward."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, op, img, mask, raw, flags, out):
+        fwd = globals()[_CURVE_BWD[op][2]]
+        if _CURVE_BWD[op][3]:
+            o, reg, ws = fwd(img, mask, raw, flags=flags, out=out, return_workspace=True)
+        else:
+            o, reg, ws = fwd(img, raw, flags=flags, return_workspace=True)
+        ctx.save_for_backward(img, raw, ws)
+        ctx.op, ctx.mask, ctx.flags = op, mask, flags
+        return o, reg
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out, grad_reg):
+        img, raw, ws = ctx.saved_tensors
+        g_img, g_raw = _curve_backward(ctx.op, img, ctx.mask, raw, grad_out.contiguous(), grad_reg, ctx.needs_input_grad[1],
+                                       workspace=ws, flags=ctx.flags)
+        return None, g_img, None, g_raw.to(raw.dtype) if ctx.needs_input_grad[3] else None, None, None
+
+
+def _curve_op_grad(op, img, mask, raw, flags, out=None):
+    if flags & F_PWL:
+        raise NotImplementedError(f"curl_amd: {op} with F_PWL (the paper's piecewise-linear curves) has no backward; "
+                                  "use torch.no_grad() or the default affine form")
+    return _CurveOpFn.apply(op, img, mask, raw, flags, out)
+
+
+class _ConvertFn(torch.autograd.Function):
+    """Autograd node of a stand-alone colour converter: forward = the no-grad call, backward = curl_<name>_bwd_f32."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, name, img, flags):
+        ctx.save_for_backward(img)
+        ctx.name = name
+        return globals()["_" + name](img, flags)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        (img,) = ctx.saved_tensors
+        return None, _convert_backward(ctx.name, img, grad_out.contiguous()), None
 
 
 # ------------------------------------------------------------------ polynomial path (model.py:206-520)

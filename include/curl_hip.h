@@ -99,7 +99,7 @@ enum {
 #define CURL_F_DIAG_NO_MEM 0x10000u   /* DIAGNOSTICS ONLY: inputs synthesised in registers, stores suppressed --
                                          times the arithmetic alone; the output buffer is left untouched */
 
-#define CURL_F_WS_READY 0x40000u /* curl_layer_bwd_f32: `workspace` is the buffer curl_layer_fwd_f32 (or an earlier backward) was
+#define CURL_F_WS_READY 0x40000u /* curl_layer_bwd_f32 (and the stage backward entries): `workspace` is the buffer curl_layer_fwd_f32 (or an earlier backward) was
                                     handed for the SAME raw knots and has not been written since: it already holds the
                                     exp'd knots and collapsed curves, the knot-prep launch is skipped.  Every prepared row
                                     carries a stamp of the knot count and row stride it was filled for: a row nobody filled
@@ -210,6 +210,50 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind,
                        void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                        int B, int H, int W, int Kl, int Kr, int Kh,
                        unsigned flags, curl_stream_t stream);
+
+/* Backward of the stand-alone curve ops, converters and fused stages above: what torch autograd runs through the
+ * reference's plain-torch curves.py / colors.py functions.  Same two passes as curl_layer_bwd_f32 (one over the pixels,
+ * forward recomputed in registers; one per image for the knots), for one knot segment.
+ * Curve and stage entries: the forward's inputs, then grad_out [B,3,H,W] (required), grad_reg [B] (nullable = zeros),
+ * grad_img [B,3,H,W] (nullable: the chain then stops at the curves' sums), grad_raw shaped like raw (ASSIGNED, required).
+ * workspace: curl_workspace_bytes(B, n_knots of the segment); scratch: curl_layer_bwd_scratch_bytes(B,H,W) bytes.
+ * flags: CURL_F_WS_READY (the workspace the forward call filled for the same knots: the knot-prep launch is skipped;
+ * rows are stamp-checked as in curl_layer_bwd_f32), CURL_F_MASK_FIRST (stages); CURL_F_PWL has no backward
+ * (CURL_E_FLAGS).  No mask gradient.  Results are reproducible: no float atomics. */
+/* replaces: autograd through curves.adjust_rgb / adjust_lab / adjust_hsv  curves.py:90-133 / 136-180 / 41-87 */
+int curl_adjust_rgb_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, int B, int H, int W, int K,
+                            unsigned flags, curl_stream_t stream);
+int curl_adjust_lab_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, int B, int H, int W, int K,
+                            unsigned flags, curl_stream_t stream);
+int curl_adjust_hsv_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
+                            float* grad_img, float* grad_raw, void* workspace, size_t workspace_bytes,
+                            void* scratch, size_t scratch_bytes, int B, int H, int W, int K,
+                            unsigned flags, curl_stream_t stream);
+/* replaces: autograd through colors.RGB2LAB.forward colors.py:27-62 ; LAB2RGB.forward colors.py:88-123 ;
+ *           RGB2HSV.forward colors.py:195-242 ; HSV2RGB.forward colors.py:131-177.
+ * grad_in [B,3,H,W] is assigned d loss / d in (all three pointers required).  flags: tuning bits only. */
+int curl_rgb2lab_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream);
+int curl_lab2rgb_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream);
+int curl_rgb2hsv_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream);
+int curl_hsv2rgb_bwd_f32(const float* in, const float* grad_out, float* grad_in, int B, int H, int W, unsigned flags,
+                         curl_stream_t stream);
+/* replaces: autograd through model.py:151-157 (rgb2lab -> adjust_lab -> *mask -> lab2rgb) and model.py:163-169 (rgb2hsv ->
+ *           adjust_hsv -> *mask -> hsv2rgb), the forwards of curl_lab_stage_f32 / curl_hsv_stage_f32. */
+int curl_lab_stage_bwd_f32(const float* img, const void* mask, int mask_kind, const float* rawL,
+                           const float* grad_out, const float* grad_reg, float* grad_img, float* grad_rawL,
+                           void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                           int B, int H, int W, int Kl, unsigned flags, curl_stream_t stream);
+int curl_hsv_stage_bwd_f32(const float* img, const void* mask, int mask_kind, const float* rawH,
+                           const float* grad_out, const float* grad_reg, float* grad_img, float* grad_rawH,
+                           void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                           int B, int H, int W, int Kh, unsigned flags, curl_stream_t stream);
 
 /* replaces: TriSpaceRegNet.generate_residual + generate_image  model.py:499-520 -- the per-pixel path of the
  *           fork's live model (infer.py:44-45, main.py:283) -- with polylayer = Deg4MobilePolyLayer
