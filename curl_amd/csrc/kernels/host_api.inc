@@ -396,6 +396,14 @@ static int check_ws(const void* ws, size_t bytes, int B, int n_knots) {
   if (bytes < curl_workspace_bytes(B, n_knots)) return fail(CURL_E_WORKSPACE, "workspace too small");
   return 0;
 }
+// the fused layer's three knot segments: L and R of 3 curves, H of 4
+static int check_layer_knots(const float* rawL, const float* rawR, const float* rawH, int Kl, int Kr, int Kh, bool uneven_ok) {
+  if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
+  if (int rc = check_K(Kl, uneven_ok)) return rc;
+  if (int rc = check_K(Kr, uneven_ok)) return rc;
+  return check_K(Kh, uneven_ok);
+}
+static int layer_n_knots(int Kl, int Kr, int Kh) { return KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4); }
 
 template <int VEC>
 static hipError_t launch_chain_u(const Geometry& g, const ChainArgs& a, hipStream_t s) {
@@ -523,6 +531,21 @@ static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, con
   return hipGetLastError();
 }
 
+// What the backward entry points share once their own knot arguments are checked: the remaining argument checks, before
+// any HIP call, then the knot prep -- unless CURL_F_WS_READY: the workspace is the one the forward filled for THESE knots
+// (the autograd nodes keep it), and the prep launch and its kernel boundary go (a fifth of a training-crop-batch backward).
+static int bwd_prologue(const float* img, const float* grad_out, const void* mask, int mask_kind, unsigned flags,
+                        const void* workspace, size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int B, int H,
+                        int W, int n_knots, const PrepArgs& prep, hipStream_t s) {
+  if (int rc = check_img(img, grad_out, B, H, W)) return rc;
+  if (int rc = check_mask(mask, mask_kind)) return rc;
+  if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;  // (+ CURL_F_MASK_FIRST, CURL_F_TUNE_PREP: allowed everywhere)
+  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
+  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_layer_bwd_scratch_bytes(B, H, W))
+    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes");
+  return (flags & CURL_F_WS_READY) ? 0 : launch_prep(prep, B, s);
+}
+
 // The backward of one knot segment of 3 (adjust_rgb / adjust_lab, the Lab stage) or 4 curves (adjust_hsv, the HSV stage):
 // arguments checked before any HIP call, the knot prep unless CURL_F_WS_READY, stage_bwd_kernel, stage_knots_bwd_kernel.
 template <int OP>
@@ -532,22 +555,17 @@ static int stage_bwd_common(const float* img, const void* mask, int mask_kind, c
                             curl_stream_t stream, const char* name) {
   constexpr int NC = StageCurves<OP>::kN;
   g_err[0] = 0;
-  if (int rc = check_img(img, grad_out, B, H, W)) return rc;
   if (!raw) return fail(CURL_E_NULL, "raw knot pointer is NULL");
   if (!grad_raw) return fail(CURL_E_NULL, "grad_raw is NULL");
-  if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_K(K, true)) return rc;
   if (flags & CURL_F_PWL) return fail(CURL_E_FLAGS, "CURL_F_PWL has no backward");
-  if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;
-  const int n_knots = KP_TOTAL(K, NC);
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
-  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_layer_bwd_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
+  const int n_knots = KP_TOTAL(K, NC);
   const unsigned stride = ws_stride(n_knots);
-  if (!(flags & CURL_F_WS_READY))
-    if (int rc = run_prep(raw, NC, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, nullptr, B, s)) return rc;
+  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
+                            n_knots, make_prep(raw, NC, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, nullptr), s))
+    return rc;
   const size_t HW = (size_t)H * W;
   const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
   StageBwdArgs a;
@@ -755,14 +773,11 @@ static int layer_fwd_impl(const float* img, const void* mask, int mask_kind, con
                           const float* rawH, float* out, float* reg, void* workspace, size_t workspace_bytes, int B, int H,
                           int W, int Kl, int Kr, int Kh, unsigned flags, curl_stream_t stream, Slab slab) {
   if (int rc = check_img(img, out, B, H, W)) return rc;
-  if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
   // (CURL_F_DIAG_SKIP_PREP: accepted by these two entries only -- it makes the kernel read a workspace the caller vouches for)
   if (int rc = check_flags(flags, CURL_F_PWL | CURL_F_EXACT_ORDER | CURL_F_DIAG_SKIP_PREP)) return rc;
-  if (int rc = check_K(Kl, chain_mode(flags) == 0)) return rc;
-  if (int rc = check_K(Kr, chain_mode(flags) == 0)) return rc;
-  if (int rc = check_K(Kh, chain_mode(flags) == 0)) return rc;
-  int n_knots = KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4);
+  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, chain_mode(flags) == 0)) return rc;
+  int n_knots = layer_n_knots(Kl, Kr, Kh);
   if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -807,13 +822,10 @@ int curl_layer_fwd_u8hwc(const uint8_t* img, const void* mask, int mask_kind, co
                          curl_stream_t stream) {
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
-  if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
+  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
-  if (int rc = check_K(Kl, true)) return rc;
-  if (int rc = check_K(Kr, true)) return rc;
-  if (int rc = check_K(Kh, true)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point");
-  int n_knots = KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4);
+  int n_knots = layer_n_knots(Kl, Kr, Kh);
   if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -836,29 +848,17 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
                        void* scratch, size_t scratch_bytes, int B, int H, int W, int Kl, int Kr, int Kh, unsigned flags,
                        curl_stream_t stream) {
   g_err[0] = 0;
-  if (int rc = check_img(img, grad_out, B, H, W)) return rc;
-  if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
+  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
   if (!grad_rawL || !grad_rawR || !grad_rawH) return fail(CURL_E_NULL, "grad_rawL/R/H must all be non-NULL");
-  if (int rc = check_mask(mask, mask_kind)) return rc;
-  if (int rc = check_K(Kl, true)) return rc;
-  if (int rc = check_K(Kr, true)) return rc;
-  if (int rc = check_K(Kh, true)) return rc;
-  if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;  // (+ CURL_F_MASK_FIRST, CURL_F_TUNE_PREP: allowed everywhere)
-  int n_knots = KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4);
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
-  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_layer_bwd_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  unsigned stride = ws_stride(n_knots);
-  // CURL_F_WS_READY: the workspace is the one curl_layer_fwd_f32 filled for THESE knots (the autograd node keeps it): the
-  // prep launch and its kernel boundary go -- a fifth of a training-crop-batch backward
-  if (!(flags & CURL_F_WS_READY))
-    if (int rc = run_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr, B, s)) return rc;
-  size_t HW = (size_t)H * W;
-  bool aligned = (HW % 4 == 0) && (((uintptr_t)img | (uintptr_t)grad_out | (uintptr_t)grad_img) % 16 == 0);
-  if (mask_kind == CURL_MASK_F32 && ((uintptr_t)mask % 16)) aligned = false;
-  if (mask_kind == CURL_MASK_U8 && ((uintptr_t)mask % 4)) aligned = false;
+  const int n_knots = layer_n_knots(Kl, Kr, Kh);
+  const unsigned stride = ws_stride(n_knots);
+  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
+                            n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s))
+    return rc;
+  const size_t HW = (size_t)H * W;
+  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
   BwdArgs a;
   a.in = img;
   a.gout = grad_out;
@@ -892,15 +892,7 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
     if (grad_img) hipLaunchKernelGGL((layer_bwd_kernel<V, M, true>), grid, block, 0, s, a);     \
     else hipLaunchKernelGGL((layer_bwd_kernel<V, M, false>), grid, block, 0, s, a);             \
   } while (0)
-  if (aligned) {
-    if (mask_kind == CURL_MASK_U8) LAUNCH_BWD(4, CURL_MASK_U8);
-    else if (mask_kind == CURL_MASK_F32) LAUNCH_BWD(4, CURL_MASK_F32);
-    else LAUNCH_BWD(4, CURL_MASK_NONE);
-  } else {
-    if (mask_kind == CURL_MASK_U8) LAUNCH_BWD(1, CURL_MASK_U8);
-    else if (mask_kind == CURL_MASK_F32) LAUNCH_BWD(1, CURL_MASK_F32);
-    else LAUNCH_BWD(1, CURL_MASK_NONE);
-  }
+  DISPATCH_VEC_MASK(LAUNCH_BWD, aligned, mask_kind);
 #undef LAUNCH_BWD
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "layer_bwd_kernel");
@@ -1278,13 +1270,10 @@ int curl_layer_loss_fwd_f32(const float* img, const void* mask, int mask_kind, c
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!target || !sums) return fail(CURL_E_NULL, "target / sums is NULL");
-  if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
+  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_flags(flags, 0)) return rc;
-  if (int rc = check_K(Kl, true)) return rc;
-  if (int rc = check_K(Kr, true)) return rc;
-  if (int rc = check_K(Kh, true)) return rc;
-  const int n_knots = KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4);
+  const int n_knots = layer_n_knots(Kl, Kr, Kh);
   if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
   if (!scratch || scratch_bytes < curl_loss_terms_scratch_bytes(B, H, W))
     return fail(CURL_E_WORKSPACE, "scratch missing or smaller than curl_loss_terms_scratch_bytes");

@@ -486,6 +486,31 @@ class TriSpaceRegNet(nn.Module):
 # ---------------------------------------------------------------------------------------------------------
 # CURLLoss (model.py:35-118): the four per-pixel terms in one fused HIP pass (+ backward); MS-SSIM is injected.
 # ---------------------------------------------------------------------------------------------------------
+def _loss_terms(sums, mask, shape):
+    """-> CURLLoss' four pointwise terms (model.py:89-109) in float32, and the unmasked count and n they divide by."""
+    s = sums.sum(0)
+    n = float(shape[0] * shape[2] * shape[3])
+    # A one-image mask ([1,1,H,W] or [1,H,W]: ops._mask) is expanded over the batch for the kernel: its sum s[4] and its
+    # zeros are then counted `rep` times.  model.py:90 takes mask.sum() of the mask AS GIVEN (so the three L1 terms are rep
+    # times larger than with a [B,1,H,W] copy), while model.py:98's mean runs over the broadcast tensor (zeros per image).
+    rep = 1 if mask is None else shape[0] // mask.shape[0]
+    unmasked = 3.0 * s[4] / rep
+    rgb, lab, hsv = s[0] / unmasked, s[2] / unmasked, s[3] / unmasked
+    # model.py:98 adds torch.logical_not(mask) -- 1 where the mask is EXACTLY 0 -- and takes the mean over the broadcast
+    # [B,B,H,W].  bool / uint8 masks (data.py:190): their zeros are n - sum; a float mask with values strictly inside
+    # (0, 1) has none of those counted, so its zeros are counted as such (on the mask as given, times `rep`).
+    n_zero = (mask == 0).sum().double() * rep if (mask is not None and mask.is_floating_point()) else n - s[4]
+    cosine = 1.0 - s[1] / n - n_zero / n
+    return rgb.float(), cosine.float(), lab.float(), hsv.float(), unmasked, n
+
+
+def _loss_pullback(pred, target, mask, grads, unmasked, n, g_Lp):
+    """d loss / d pred of _loss_terms, given the gradients reaching its four terms (None counts as 0) and the L plane's."""
+    g = [torch.zeros((), dtype=torch.float64, device=unmasked.device) if x is None else x.double() for x in grads]
+    w = torch.stack((g[0] / unmasked, -g[1] / n, g[2] / unmasked, g[3] / unmasked)).to(torch.float32)
+    return ops.loss_terms_backward(pred, target, mask, w, g_Lp)
+
+
 class _LossTermsFn(torch.autograd.Function):
     """(pred, target, mask) -> (rgb_l1, cosine, lab_l1, hsv_l1, L_pred, L_target) as in model.py:89-109."""
 
@@ -493,33 +518,17 @@ class _LossTermsFn(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, pred, target, mask):
         sums, Lp, Lt = ops.loss_term_sums(pred, target, mask)
-        s = sums.sum(0)
-        n = float(pred.shape[0] * pred.shape[2] * pred.shape[3])
-        # A mask of ONE image ([1,1,H,W] or [1,H,W]: ops._mask) is expanded over the batch for the
-        # kernel: its sum s[4] and its zeros are then counted `rep` times.  model.py:90 takes mask.sum() of the mask AS GIVEN
-        # (so the three L1 terms are rep times larger than with a [B,1,H,W] copy of it), while model.py:98's mean runs over
-        # the broadcast tensor (zeros counted per image).
-        rep = 1 if mask is None else pred.shape[0] // mask.shape[0]
-        unmasked = 3.0 * s[4] / rep
-        rgb, lab, hsv = s[0] / unmasked, s[2] / unmasked, s[3] / unmasked
-        # model.py:98 adds torch.logical_not(mask) -- 1 where the mask is EXACTLY 0 -- and takes the mean over the broadcast
-        # [B,B,H,W].  bool / uint8 masks (data.py:190): their zeros are n - sum; a float mask with values strictly inside
-        # (0, 1) has none of those counted, so its zeros are counted as such (on the mask as given, times `rep`).
-        n_zero = (mask == 0).sum().double() * rep if (mask is not None and mask.is_floating_point()) else n - s[4]
-        cosine = 1.0 - s[1] / n - n_zero / n
+        rgb, cosine, lab, hsv, unmasked, n = _loss_terms(sums, mask, pred.shape)
         ctx.save_for_backward(pred, target, unmasked)
         ctx.mask, ctx.n = mask, n
         ctx.mark_non_differentiable(Lt)
-        f = torch.float32
-        return rgb.to(f), cosine.to(f), lab.to(f), hsv.to(f), Lp, Lt
+        return rgb, cosine, lab, hsv, Lp, Lt
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_rgb, g_cos, g_lab, g_hsv, g_Lp, _g_Lt):
         pred, target, unmasked = ctx.saved_tensors
-        w = torch.stack((g_rgb.double() / unmasked, -g_cos.double() / ctx.n, g_lab.double() / unmasked,
-                         g_hsv.double() / unmasked)).to(torch.float32)
-        return ops.loss_terms_backward(pred, target, ctx.mask, w, g_Lp), None, None
+        return _loss_pullback(pred, target, ctx.mask, (g_rgb, g_cos, g_lab, g_hsv), unmasked, ctx.n, g_Lp), None, None
 
 
 class _LayerLossFn(torch.autograd.Function):
@@ -532,28 +541,18 @@ class _LayerLossFn(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, img, mask, L, R, H, target):
         out, reg, sums, Lp, Lt, ws = ops.layer_loss_forward(img, mask, L, R, H, target)
-        s = sums.sum(0)
-        n = float(out.shape[0] * out.shape[2] * out.shape[3])
-        rep = 1 if mask is None else out.shape[0] // mask.shape[0]  # a one-image mask broadcast over the batch: _LossTermsFn
-        unmasked = 3.0 * s[4] / rep
-        rgb, lab, hsv = s[0] / unmasked, s[2] / unmasked, s[3] / unmasked
-        n_zero = (mask == 0).sum().double() * rep if (mask is not None and mask.is_floating_point()) else n - s[4]
-        cosine = 1.0 - s[1] / n - n_zero / n  # model.py:98 (see _LossTermsFn)
+        rgb, cosine, lab, hsv, unmasked, n = _loss_terms(sums, mask, out.shape)
         ctx.save_for_backward(img, L.contiguous(), R.contiguous(), H.contiguous(), ws, out, target, unmasked)
         ctx.mask, ctx.n = mask, n
         ctx.mark_non_differentiable(Lt)
         ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a zero image to be added
-        f = torch.float32
-        return out, reg, rgb.to(f), cosine.to(f), lab.to(f), hsv.to(f), Lp, Lt
+        return out, reg, rgb, cosine, lab, hsv, Lp, Lt
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_out, g_reg, g_rgb, g_cos, g_lab, g_hsv, g_Lp, _g_Lt):
         img, L, R, H, ws, out, target, unmasked = ctx.saved_tensors
-        zero = torch.zeros((), dtype=torch.float64, device=out.device)
-        d = lambda g: zero if g is None else g.double()  # noqa: E731
-        w = torch.stack((d(g_rgb) / unmasked, -d(g_cos) / ctx.n, d(g_lab) / unmasked, d(g_hsv) / unmasked)).to(torch.float32)
-        g_pred = ops.loss_terms_backward(out, target, ctx.mask, w, g_Lp)
+        g_pred = _loss_pullback(out, target, ctx.mask, (g_rgb, g_cos, g_lab, g_hsv), unmasked, ctx.n, g_Lp)
         if g_out is not None:
             g_pred = g_pred + g_out
         g_img, gL, gR, gH = ops.curl_layer_backward(img, ctx.mask, L, R, H, g_pred, g_reg, ctx.needs_input_grad[0], workspace=ws)

@@ -12,6 +12,11 @@ from . import _lib
 from ._lib import F_EXACT_ORDER, F_MASK_FIRST, F_PWL, MASK_F32, MASK_NONE, MASK_U8
 
 
+def _is_empty_image(img):
+    """An empty [B,3,H,W] image (B == 0 or H*W == 0): the ops answer it without a launch."""
+    return isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0
+
+
 def _empty_ok(mask_arg=None):
     """The reference's eager ops accept empty tensors ([0,3,H,W], or H*W == 0) and return empty ones; the kernels
     are never launched on zero pixels.  Ops that also return a regulariser still owe it (it depends on the knots
@@ -19,7 +24,7 @@ def _empty_ok(mask_arg=None):
     def deco(fn):
         @functools.wraps(fn)
         def wrapper(img, *args, **kwargs):
-            if not (isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0):
+            if not _is_empty_image(img):
                 return fn(img, *args, **kwargs)
             _need_device(img, "img")
             out = torch.empty_like(img)
@@ -152,6 +157,21 @@ def _knots(t, name, ncurves, B):
     if t.dtype is not torch.float32 or not t.is_contiguous():
         t = t.to(torch.float32).contiguous()
     return t, (K if K_last == K else K | (K_last << 16))
+
+
+def _layer_knots(L, R, H, B):
+    """The layer's three knot segments, checked and packed -> (Lc, Rc, Hc, Kl, Kr, Kh, n_knots)."""
+    Lc, Kl = _knots(L, "L", 3, B)
+    Rc, Kr = _knots(R, "R", 3, B)
+    Hc, Kh = _knots(H, "H", 4, B)
+    return Lc, Rc, Hc, Kl, Kr, Kh, Lc.shape[1] + Rc.shape[1] + Hc.shape[1]
+
+
+def _check_coeffs(coeffs, B):
+    """The polynomial path's [B,3,3,126|35] coefficient table (then converted by _coeffs32)."""
+    _need_device(coeffs, "coeffs")
+    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in (126, 35):
+        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)}")
 
 
 def _mask(mask, img):
@@ -338,21 +358,25 @@ def lab_stage(img, mask, L, flags=0, out=None):
     return _lab_stage(img, mask, L, flags=flags, out=out)
 
 
-@_one_device
-@_empty_ok(mask_arg=0)
-def _lab_stage(img, mask, L, flags=0, out=None, return_workspace=False):
+def _stage(fn_name, name, ncurves, img, mask, raw, flags, out, return_workspace):
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
-    Lc, Kl = _knots(L, "L", 3, B)
+    rawc, K = _knots(raw, name, ncurves, B)
     m, kind = _mask(mask, img)
     out = torch.empty_like(img) if out is None else _check_out(out, img)
     reg = torch.empty(B, dtype=torch.float32, device=img.device)
-    ws, nbytes = _workspace(B, Lc.shape[1], img.device)
-    rc = lib.curl_lab_stage_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), out.data_ptr(), reg.data_ptr(),
-                                ws.data_ptr(), nbytes, B, H, W, Kl, flags, _stream(img))
-    _lib.check(rc, "curl_lab_stage_f32")
+    ws, nbytes = _workspace(B, rawc.shape[1], img.device)
+    rc = getattr(lib, fn_name)(img.data_ptr(), _ptr(m), kind, rawc.data_ptr(), out.data_ptr(), reg.data_ptr(),
+                               ws.data_ptr(), nbytes, B, H, W, K, flags, _stream(img))
+    _lib.check(rc, fn_name)
     return (out, reg, ws) if return_workspace else (out, reg)
+
+
+@_one_device
+@_empty_ok(mask_arg=0)
+def _lab_stage(img, mask, L, flags=0, out=None, return_workspace=False):
+    return _stage("curl_lab_stage_f32", "L", 3, img, mask, L, flags, out, return_workspace)
 
 
 def hsv_stage(img, mask, H, flags=0, out=None):
@@ -366,18 +390,7 @@ def hsv_stage(img, mask, H, flags=0, out=None):
 @_one_device
 @_empty_ok(mask_arg=0)
 def _hsv_stage(img, mask, H, flags=0, out=None, return_workspace=False):
-    lib = _lib.load()
-    img = _image(img)
-    B, _, Hh, W = img.shape
-    Hc, Kh = _knots(H, "H", 4, B)
-    m, kind = _mask(mask, img)
-    out = torch.empty_like(img) if out is None else _check_out(out, img)
-    reg = torch.empty(B, dtype=torch.float32, device=img.device)
-    ws, nbytes = _workspace(B, Hc.shape[1], img.device)
-    rc = lib.curl_hsv_stage_f32(img.data_ptr(), _ptr(m), kind, Hc.data_ptr(), out.data_ptr(), reg.data_ptr(),
-                                ws.data_ptr(), nbytes, B, Hh, W, Kh, flags, _stream(img))
-    _lib.check(rc, "curl_hsv_stage_f32")
-    return (out, reg, ws) if return_workspace else (out, reg)
+    return _stage("curl_hsv_stage_f32", "H", 4, img, mask, H, flags, out, return_workspace)
 
 
 def curl_layer_forward(img, mask, L, R, H, flags=0, out=None, return_workspace=False):
@@ -405,13 +418,11 @@ def _curl_layer_forward_checked(img, mask, L, R, H, flags=0, out=None, return_wo
     lib = _lib.load()
     img = _image(img)
     B, _, Hh, W = img.shape
-    Lc, Kl = _knots(L, "L", 3, B)
-    Rc, Kr = _knots(R, "R", 3, B)
-    Hc, Kh = _knots(H, "H", 4, B)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, img)
     out = torch.empty_like(img) if out is None else _check_out(out, img)
     reg = torch.empty(B, dtype=torch.float32, device=img.device)
-    ws, nbytes = _workspace(B, Lc.shape[1] + Rc.shape[1] + Hc.shape[1], img.device)
+    ws, nbytes = _workspace(B, n_knots, img.device)
     rc = lib.curl_layer_fwd_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
                                 out.data_ptr(), reg.data_ptr(), ws.data_ptr(), nbytes, B, Hh, W, Kl, Kr, Kh,
                                 flags, _stream(img))
@@ -435,13 +446,11 @@ def curl_layer_forward_rows(img, mask, L, R, H, rows, out, flags=0):
     img = _image(img)
     B, _, Hh, W = img.shape
     r0, n = _slab(rows, Hh)
-    Lc, Kl = _knots(L, "L", 3, B)
-    Rc, Kr = _knots(R, "R", 3, B)
-    Hc, Kh = _knots(H, "H", 4, B)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, img)
     out = _check_out(out, img)
     reg = torch.empty(B, dtype=torch.float32, device=img.device)
-    ws, nbytes = _workspace(B, Lc.shape[1] + Rc.shape[1] + Hc.shape[1], img.device)
+    ws, nbytes = _workspace(B, n_knots, img.device)
     rc = lib.curl_layer_fwd_slab_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
                                      out.data_ptr(), reg.data_ptr(), ws.data_ptr(), nbytes, B, Hh, W, r0, n, Kl, Kr, Kh,
                                      flags, _stream(img))
@@ -457,15 +466,49 @@ def trispace_forward_rows(img, coeffs, rows, out, residual_only=False):
     img = _image(img)
     B, _, H, W = img.shape
     r0, n = _slab(rows, H)
-    _need_device(coeffs, "coeffs")
-    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in (126, 35):
-        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)}")
+    _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     out = _check_out(out, img)
     rc = lib.curl_trispace_fwd_slab_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, r0, n, c.shape[3],
                                         _lib.F_RESIDUAL_ONLY if residual_only else 0, _stream(img))
     _lib.check(rc, "curl_trispace_fwd_slab_f32")
     return out
+
+
+def _image_and_grad(img, grad_out):
+    """A backward's image and the gradient at its output: both [B,3,H,W] float32, the same shape."""
+    img = _image(img)
+    grad_out = _image(grad_out, "grad_out")
+    if grad_out.shape != img.shape:
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    return img, grad_out
+
+
+def _grad_reg32(grad_reg, B):
+    if grad_reg is None:
+        return None
+    _need_device(grad_reg, "grad_reg")
+    grad_reg = grad_reg.to(torch.float32).contiguous()
+    if grad_reg.shape != (B,):
+        raise ValueError("grad_reg must be [B]")
+    return grad_reg
+
+
+def _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags, ws_source):
+    """What the layer and the curve backwards share: grad_reg as float32 [B] (or None), the knot workspace -- the caller's
+    (CURL_F_WS_READY: `ws_source` filled it for the same knots, the entry point skips its knot prep) or a fresh one -- and
+    the block-partials scratch.  -> (grad_reg, ws, nbytes, bflags, scratch, sbytes)"""
+    B, _, H, W = img.shape
+    grad_reg = _grad_reg32(grad_reg, B)
+    ws, nbytes = _workspace(B, n_knots, img.device)
+    bflags = flags & F_MASK_FIRST  # the one forward flag that means something here
+    if workspace is not None:
+        if workspace.device != img.device or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
+            raise ValueError(f"workspace is not the tensor {ws_source} for this batch")
+        ws, bflags = workspace, bflags | _lib.F_WS_READY
+    sbytes = lib.curl_layer_bwd_scratch_bytes(B, H, W)
+    scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
+    return grad_reg, ws, nbytes, bflags, scratch, sbytes
 
 
 def curl_layer_backward(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
@@ -487,30 +530,14 @@ def curl_layer_backward(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_i
 @_one_device
 def _curl_layer_backward_checked(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
     lib = _lib.load()
-    img = _image(img)
-    grad_out = _image(grad_out, "grad_out")
-    if grad_out.shape != img.shape:
-        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    img, grad_out = _image_and_grad(img, grad_out)
     B, _, Hh, W = img.shape
-    Lc, Kl = _knots(L, "L", 3, B)
-    Rc, Kr = _knots(R, "R", 3, B)
-    Hc, Kh = _knots(H, "H", 4, B)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, img)
-    if grad_reg is not None:
-        _need_device(grad_reg, "grad_reg")
-        grad_reg = grad_reg.to(torch.float32).contiguous()
-        if grad_reg.shape != (B,):
-            raise ValueError("grad_reg must be [B]")
     g_img = torch.empty_like(img) if need_grad_img else None
     gL, gR, gH = torch.empty_like(Lc), torch.empty_like(Rc), torch.empty_like(Hc)
-    ws, nbytes = _workspace(B, Lc.shape[1] + Rc.shape[1] + Hc.shape[1], img.device)
-    bflags = flags & F_MASK_FIRST  # the one forward flag that means something here
-    if workspace is not None:
-        if workspace.device != img.device or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
-            raise ValueError("workspace is not the tensor curl_layer_forward returned for this batch")
-        ws, bflags = workspace, bflags | _lib.F_WS_READY
-    sbytes = lib.curl_layer_bwd_scratch_bytes(B, Hh, W)
-    scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
+    grad_reg, ws, nbytes, bflags, scratch, sbytes = _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags,
+                                                               "curl_layer_forward returned")
     rc = lib.curl_layer_bwd_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
                                 grad_out.data_ptr(), _ptr(grad_reg), _ptr(g_img), gL.data_ptr(), gR.data_ptr(),
                                 gH.data_ptr(), ws.data_ptr(), nbytes, scratch.data_ptr(), sbytes, B, Hh, W, Kl, Kr, Kh,
@@ -520,16 +547,6 @@ def _curl_layer_backward_checked(img, mask, L, R, H, grad_out, grad_reg=None, ne
 
 
 # ------------------------------------------------------------------ backward of the stand-alone curve ops and stages
-def _grad_reg32(grad_reg, B):
-    if grad_reg is None:
-        return None
-    _need_device(grad_reg, "grad_reg")
-    grad_reg = grad_reg.to(torch.float32).contiguous()
-    if grad_reg.shape != (B,):
-        raise ValueError("grad_reg must be [B]")
-    return grad_reg
-
-
 # op -> (C entry point, curves, forward, takes a mask)
 _CURVE_BWD = {
     "adjust_rgb": ("curl_adjust_rgb_bwd_f32", 3, "_adjust_rgb", False),
@@ -545,7 +562,7 @@ def _curve_backward(op, img, mask, raw, grad_out, grad_reg=None, need_grad_img=T
     """-> (grad_img or None, grad_raw): the backward of one stand-alone curve op or stage (_CURVE_BWD)."""
     fn_name, ncurves, _, masked = _CURVE_BWD[op]
     lib = _lib.load()
-    if isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0:
+    if _is_empty_image(img):
         # an empty image owes only the regulariser's share: the same entry point on a 1x1 stand-in with a zero gradient
         _need_device(img, "img")
         B = img.shape[0]
@@ -555,23 +572,13 @@ def _curve_backward(op, img, mask, raw, grad_out, grad_reg=None, need_grad_img=T
         z = img.new_zeros((B, 3, 1, 1))
         _, g_raw = _curve_backward(op, z, None, raw, z, grad_reg, False, None, flags)
         return g_img, g_raw
-    img = _image(img)
-    grad_out = _image(grad_out, "grad_out")
-    if grad_out.shape != img.shape:
-        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    img, grad_out = _image_and_grad(img, grad_out)
     B, _, Hh, W = img.shape
     rawc, K = _knots(raw, "knots", ncurves, B)
-    grad_reg = _grad_reg32(grad_reg, B)
     g_img = torch.empty_like(img) if need_grad_img else None
     g_raw = torch.empty_like(rawc)
-    ws, nbytes = _workspace(B, rawc.shape[1], img.device)
-    bflags = flags & F_MASK_FIRST
-    if workspace is not None:
-        if workspace.device != img.device or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
-            raise ValueError(f"workspace is not the tensor ops.{op} filled for this batch")
-        ws, bflags = workspace, bflags | _lib.F_WS_READY
-    sbytes = lib.curl_layer_bwd_scratch_bytes(B, Hh, W)
-    scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
+    grad_reg, ws, nbytes, bflags, scratch, sbytes = _bwd_setup(lib, img, grad_reg, rawc.shape[1], workspace, flags,
+                                                               f"ops.{op} filled")
     head = (img.data_ptr(),)
     if masked:
         m, kind = _mask(mask, img)
@@ -611,14 +618,11 @@ def hsv_stage_backward(img, mask, H, grad_out, grad_reg=None, need_grad_img=True
 
 @_one_device
 def _convert_backward(name, img, grad_out):
-    if isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] == 3 and img.numel() == 0:
+    if _is_empty_image(img):
         _need_device(img, "img")
         return torch.empty_like(img)
     lib = _lib.load()
-    img = _image(img)
-    grad_out = _image(grad_out, "grad_out")
-    if grad_out.shape != img.shape:
-        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not match img {tuple(img.shape)}")
+    img, grad_out = _image_and_grad(img, grad_out)
     B, _, H, W = img.shape
     g = torch.empty_like(img)
     fn_name = f"curl_{name}_bwd_f32"
@@ -710,9 +714,7 @@ def trispace_forward(img, coeffs, residual_only=False, flags=0):
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
-    _need_device(coeffs, "coeffs")
-    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in (126, 35):
-        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)}")
+    _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     out = torch.empty_like(img)
     rc = lib.curl_trispace_fwd_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, c.shape[3],
@@ -727,6 +729,7 @@ def trispace_backward(img, coeffs, grad_out, residual_only=False):
     lib = _lib.load()
     img, grad_out = _image(img), _image(grad_out, "grad_out")
     B, _, H, W = img.shape
+    _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     nc = c.shape[3]
     g = torch.empty_like(c)
@@ -847,9 +850,7 @@ def _trispace_forward_u8hwc_checked(img_u8, coeffs, white_mask=None):
     lib = _lib.load()
     x = _bytes_image(img_u8)
     B, H, W, _ = x.shape
-    _need_device(coeffs, "coeffs")
-    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in (126, 35):
-        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)}")
+    _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     wm = _white(white_mask, x)
     out = torch.empty_like(x)
@@ -866,14 +867,12 @@ def curl_layer_forward_u8hwc(img_u8, mask, L, R, H, white_mask=None):
     lib = _lib.load()
     x = _bytes_image(img_u8)
     B, Hh, W, _ = x.shape
-    Lc, Kl = _knots(L, "L", 3, B)
-    Rc, Kr = _knots(R, "R", 3, B)
-    Hc, Kh = _knots(H, "H", 4, B)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, SimpleNamespace(shape=(B, 3, Hh, W)))
     wm = _white(white_mask, x)
     out = torch.empty_like(x)
     reg = torch.empty(B, dtype=torch.float32, device=x.device)
-    ws, nbytes = _workspace(B, Lc.shape[1] + Rc.shape[1] + Hc.shape[1], x.device)
+    ws, nbytes = _workspace(B, n_knots, x.device)
     rc = lib.curl_layer_fwd_u8hwc(x.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(), _ptr(wm),
                                   out.data_ptr(), reg.data_ptr(), ws.data_ptr(), nbytes, B, Hh, W, Kl, Kr, Kh, 0,
                                   _stream(x))
@@ -974,16 +973,14 @@ def layer_loss_forward(img, mask, L, R, H, target, want_L=True):
     if img.shape != target.shape:
         raise ValueError("img and target must have the same shape")
     B, _, Hh, W = img.shape
-    Lc, Kl = _knots(L, "L", 3, B)
-    Rc, Kr = _knots(R, "R", 3, B)
-    Hc, Kh = _knots(H, "H", 4, B)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, img)
     out = torch.empty_like(img)
     reg = torch.empty(B, dtype=torch.float32, device=img.device)
     sums = torch.empty(B, 5, dtype=torch.float64, device=img.device)
     Lp = torch.empty(B, 1, Hh, W, dtype=torch.float32, device=img.device) if want_L else None
     Lt = torch.empty_like(Lp) if want_L else None
-    ws, nbytes = _workspace(B, Lc.shape[1] + Rc.shape[1] + Hc.shape[1], img.device)
+    ws, nbytes = _workspace(B, n_knots, img.device)
     sbytes = lib.curl_loss_terms_scratch_bytes(B, Hh, W)
     scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
     rc = lib.curl_layer_loss_fwd_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(), target.data_ptr(),

@@ -91,6 +91,71 @@ def test_argument_errors_are_codes_not_crashes():
         _lib.check(-2, "x")
 
 
+def _layer_args(lib, name, B=1, H=4, W=4, K=16, **kw):
+    """Valid-looking arguments of a layer entry point (fake device pointers: every call below must fail before any use)."""
+    fake = ctypes.c_void_p(4096)
+    a = dict(img=fake, mask=None, kind=0, rawL=fake, rawR=fake, rawH=fake, out=fake, reg=fake, white=None, gout=fake,
+             greg=None, gimg=fake, gL=fake, gR=fake, gH=fake, target=fake, sums=fake, Lp=None, Lt=None,
+             ws=fake, ws_bytes=lib.curl_workspace_bytes(B, 10 * K), scratch=fake, B=B, H=H, W=W, row0=0, rows=H,
+             Kl=K, Kr=K, Kh=K, flags=0)
+    a["scratch_bytes"] = (lib.curl_loss_terms_scratch_bytes if "loss" in name else lib.curl_layer_bwd_scratch_bytes)(B, H, W)
+    a.update(kw)
+    knots, tail = [a["rawL"], a["rawR"], a["rawH"]], [a["Kl"], a["Kr"], a["Kh"], a["flags"], None]
+    head = [a["img"], a["mask"], a["kind"]] + knots
+    if name == "curl_layer_fwd_f32":
+        return head + [a["out"], a["reg"], a["ws"], a["ws_bytes"], a["B"], a["H"], a["W"]] + tail
+    if name == "curl_layer_fwd_slab_f32":
+        return head + [a["out"], a["reg"], a["ws"], a["ws_bytes"], a["B"], a["H"], a["W"], a["row0"], a["rows"]] + tail
+    if name == "curl_layer_fwd_u8hwc":
+        return head + [a["white"], a["out"], a["reg"], a["ws"], a["ws_bytes"], a["B"], a["H"], a["W"]] + tail
+    if name == "curl_layer_bwd_f32":
+        return head + [a["gout"], a["greg"], a["gimg"], a["gL"], a["gR"], a["gH"], a["ws"], a["ws_bytes"], a["scratch"],
+                       a["scratch_bytes"], a["B"], a["H"], a["W"]] + tail
+    assert name == "curl_layer_loss_fwd_f32"
+    return head + [a["target"], a["out"], a["reg"], a["sums"], a["Lp"], a["Lt"], a["ws"], a["ws_bytes"], a["scratch"],
+                   a["scratch_bytes"], a["B"], a["H"], a["W"]] + tail
+
+
+def test_layer_entry_points_report_each_single_fault():
+    """One argument list per fault for the five entry points that take the L/R/H knot triple: each returns the code and
+    the curl_last_error text it always has, before any HIP call."""
+    from curl_amd import _lib
+    lib = _lib.load()
+    E_NULL, E_KNOTS, E_WORKSPACE, E_MASK, E_FLAGS = -1, -3, -4, -5, -6
+    fake, odd = ctypes.c_void_p(4096), ctypes.c_void_p(4096 + 4)
+    common = [(dict(rawL=None), E_NULL, b"rawL/rawR/rawH"), (dict(rawR=None), E_NULL, b"rawL/rawR/rawH"),
+              (dict(rawH=None), E_NULL, b"rawL/rawR/rawH")]
+    for k in ("Kl", "Kr", "Kh"):
+        common += [({k: 1}, E_KNOTS, b"knots per curve"), ({k: 300}, E_KNOTS, b"knots per curve"),
+                   ({k: -1}, E_KNOTS, b"knots per curve"), ({k: 16 | (17 << 16)}, E_KNOTS, b"last curve")]
+    common += [(dict(kind=7, mask=fake), E_MASK, b"mask_kind must be"), (dict(kind=1, mask=None), E_MASK, b"mask pointer"),
+               (dict(kind=2, mask=None), E_MASK, b"mask pointer"), (dict(flags=_lib.F_RESIDUAL_ONLY), E_FLAGS, b"flag bit"),
+               (dict(ws=None), E_WORKSPACE, b"workspace is NULL"), (dict(ws=odd), E_WORKSPACE, b"16-byte aligned"),
+               (dict(ws_bytes=16), E_WORKSPACE, b"too small")]
+    scratch = [(dict(scratch=None), E_WORKSPACE, b"scratch"), (dict(scratch_bytes=4), E_WORKSPACE, b"scratch")]
+    only = {
+        "curl_layer_fwd_f32": [({"Kh": 16 | (8 << 16), "flags": _lib.F_EXACT_ORDER}, E_KNOTS, b"CURL_K_UNEVEN"),
+                               ({"Kl": 16 | (8 << 16), "flags": _lib.F_PWL}, E_KNOTS, b"CURL_K_UNEVEN"),
+                               (dict(flags=_lib.F_WS_READY), E_FLAGS, b"flag bit"),
+                               (dict(flags=_lib.F_EXACT_ORDER | _lib.F_PWL), E_FLAGS, b"exclusive")],
+        "curl_layer_fwd_slab_f32": [({"Kr": 16 | (8 << 16), "flags": _lib.F_EXACT_ORDER}, E_KNOTS, b"CURL_K_UNEVEN"),
+                                    (dict(flags=_lib.F_WS_READY), E_FLAGS, b"flag bit")],
+        "curl_layer_fwd_u8hwc": [(dict(flags=_lib.F_MASK_FIRST), E_FLAGS, b"flag bit")],
+        "curl_layer_bwd_f32": scratch + [
+            (dict(scratch=odd), E_WORKSPACE, b"misaligned"), (dict(gL=None), E_NULL, b"grad_rawL/R/H"),
+            (dict(gR=None), E_NULL, b"grad_rawL/R/H"), (dict(gH=None), E_NULL, b"grad_rawL/R/H"),
+            (dict(flags=_lib.F_PWL), E_FLAGS, b"flag bit"), (dict(flags=_lib.F_DIAG_SKIP_PREP), E_FLAGS, b"flag bit")],
+        "curl_layer_loss_fwd_f32": scratch + [
+            (dict(target=None), E_NULL, b"target / sums"), (dict(sums=None), E_NULL, b"target / sums"),
+            (dict(flags=_lib.F_PWL), E_FLAGS, b"flag bit")],
+    }
+    for name, own in only.items():
+        fn = getattr(lib, name)
+        for kw, code, word in common + own:
+            assert fn(*_layer_args(lib, name, **kw)) == code, (name, kw, lib.curl_last_error())
+            assert word in lib.curl_last_error(), (name, kw, lib.curl_last_error())
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     """No fallback: a missing .so is an ImportError naming the build command."""
     import importlib

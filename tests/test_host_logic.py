@@ -280,6 +280,49 @@ def test_out_argument_is_validated():
         ops._check_out([1, 2], img)
 
 
+def test_coefficient_table_is_validated(monkeypatch):
+    """A malformed [B,3,3,126|35] table is refused in Python, with the batch named, by the polynomial forwards and backward."""
+    monkeypatch.setattr(ops, "_need_device", lambda t, name: None)
+    img, u8 = torch.zeros(2, 3, 4, 4), torch.zeros(2, 4, 4, 3, dtype=torch.uint8)
+    for bad in (torch.zeros(2, 3, 126), torch.zeros(1, 3, 3, 126), torch.zeros(2, 3, 2, 35), torch.zeros(2, 3, 3, 100)):
+        for call in (lambda: ops.trispace_forward(img, bad), lambda: ops.trispace_forward_rows(img, bad, (0, 2), img.clone()),
+                     lambda: ops._trispace_forward_u8hwc_checked(u8, bad), lambda: ops.trispace_backward(img, bad, img)):
+            with pytest.raises(ValueError, match=r"coeffs must be \[B=2,3,3,126\|35\], got"):
+                call()
+
+
+def test_backward_argument_errors(monkeypatch):
+    """The checks the layer backward and the curve / stage backwards share, each with the message its caller has always
+    raised (the workspace names the forward that fills it)."""
+    monkeypatch.setattr(ops, "_need_device", lambda t, name: None)
+    img, L, R, H = torch.zeros(2, 3, 4, 4), torch.zeros(2, 48), torch.zeros(2, 48), torch.zeros(2, 64)
+    layer = lambda **kw: ops.curl_layer_backward(img, None, L, R, H, kw.pop("g", img), **kw)  # noqa: E731
+    stage = lambda **kw: ops.lab_stage_backward(img, None, L, kw.pop("g", img), **kw)  # noqa: E731
+    adjust = lambda **kw: ops.adjust_hsv_backward(img, H, kw.pop("g", img), **kw)  # noqa: E731
+    for call in (layer, stage, adjust):
+        with pytest.raises(ValueError, match=r"grad_out \(2, 3, 4, 2\) does not match img \(2, 3, 4, 4\)"):
+            call(g=torch.zeros(2, 3, 4, 2))
+        with pytest.raises(ValueError, match=r"grad_reg must be \[B\]"):
+            call(grad_reg=torch.zeros(3))
+    for call, who in ((layer, "curl_layer_forward"), (stage, "ops.lab_stage"), (adjust, "ops.adjust_hsv")):
+        for ws in (torch.zeros(4), torch.zeros(1 << 16, dtype=torch.float64)):
+            with pytest.raises(ValueError, match=f"workspace is not the tensor {who}"):
+                call(workspace=ws)
+    with pytest.raises(ValueError, match=r"grad_out \(2, 3, 4, 2\) does not match img"):
+        ops.rgb2hsv_backward(img, torch.zeros(2, 3, 4, 2))
+
+
+def test_backward_of_an_empty_image(monkeypatch):
+    monkeypatch.setattr(ops, "_need_device", lambda t, name: None)
+    e = torch.zeros(0, 3, 4, 4)
+    for fn in (ops.rgb2lab_backward, ops.lab2rgb_backward, ops.rgb2hsv_backward, ops.hsv2rgb_backward):
+        assert fn(e, e).shape == e.shape
+    g_img, g_L = ops.lab_stage_backward(e, None, torch.zeros(0, 48), e)
+    assert g_img.shape == e.shape and g_L.shape == (0, 48) and not g_L.any()
+    g_img, g_S = ops.adjust_hsv_backward(e, torch.zeros(0, 64), e, need_grad_img=False)
+    assert g_img is None and g_S.shape == (0, 64)
+
+
 class _RandProbe(torch.utils.data.Dataset):
     """Reports the augmentation draws a data.Dataset makes inside DataLoader workers."""
 

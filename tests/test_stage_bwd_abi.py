@@ -47,14 +47,18 @@ def test_argument_errors_are_codes():
                                (dict(flags=F_PWL), E_FLAGS, b"PWL"), (dict(flags=F_PWL | F_WS_READY), E_FLAGS, b"PWL"),
                                (dict(flags=0x1), E_FLAGS, b"flag"),
                                (dict(ws=None), E_WORKSPACE, b"workspace"), (dict(ws_bytes=16), E_WORKSPACE, b"small"),
-                               (dict(scratch=None), E_WORKSPACE, b"scratch"), (dict(scratch_bytes=4), E_WORKSPACE, b"scratch")):
+                               (dict(ws=ctypes.c_void_p(4100)), E_WORKSPACE, b"aligned"),
+                               (dict(scratch=None), E_WORKSPACE, b"scratch"), (dict(scratch_bytes=4), E_WORKSPACE, b"scratch"),
+                               (dict(scratch=ctypes.c_void_p(4100)), E_WORKSPACE, b"misaligned"),
+                               (dict(K=16 | (17 << 16)), E_KNOTS, b"last curve")):
             assert fn(*_stage_args(lib, name, **kw)) == code, (name, kw)
             assert word in lib.curl_last_error(), (name, kw, lib.curl_last_error())
     for name in ("curl_lab_stage_bwd_f32", "curl_hsv_stage_bwd_f32"):
         fn = getattr(lib, name)
         assert fn(*_stage_args(lib, name, kind=7, mask=ctypes.c_void_p(4096))) == E_MASK  # bad mask kind
+        assert b"mask_kind must be" in lib.curl_last_error()
         assert fn(*_stage_args(lib, name, kind=1, mask=None)) == E_MASK  # kind set, pointer NULL
-        assert b"mask" in lib.curl_last_error()
+        assert b"mask pointer" in lib.curl_last_error()
     fake = ctypes.c_void_p(4096)
     for name in ("curl_rgb2lab_bwd_f32", "curl_lab2rgb_bwd_f32", "curl_rgb2hsv_bwd_f32", "curl_hsv2rgb_bwd_f32"):
         fn = getattr(lib, name)
