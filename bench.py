@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on the MI355X: Mpix/s through the fused curve-apply at
-1500x1000, batch 32 per GPU, plus PSNR delta vs the reference arithmetic (the oracle).
+1500x1000, batch 32 per GPU, plus (--full) PSNR delta vs the reference arithmetic (the oracle).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N=1 runs in this process.  N>1 under torch.distributed.run (RANK/WORLD_SIZE set: how the driver starts it) is one
 rank per GPU; N>1 started plainly launches `python -m torch.distributed.run --nproc-per-node N bench.py ...`
@@ -12,10 +12,15 @@ ITSELF as a child process -- before anything touches the GPU -- relays its outpu
 A step = one pass of the hot path over one batch: CURLLayer.forward (model.py:137-176) as the fused
 HIP kernel (RGB->Lab->curves->RGB->curves->HSV->curves->RGB + residual), inputs resident in HBM.
 Batches shard by image across ranks with NO data-path collective (weak scaling, 32 images per GPU).
-Rank 0 prints ONE compact JSON line on stdout (make_line: the contract's keys, `roofline`, `cpu_baseline`, four accuracy
-scalars and the literal-protocol figure; <= 4 KB, strict JSON -- tests/test_host_logic.py holds it to that).  Everything
-else (the other workloads' rows, the end-to-end and train-step records, the full accuracy block, board power) goes to
-bench_detail.json (beside this file and under gpurun_out/) and to stderr, never stdout.
+Rank 0 prints ONE compact JSON line on stdout (make_line: the contract's keys and the headline's `roofline`; <= 4 KB, strict
+JSON -- tests/test_host_logic.py holds it to that).
+
+A plain run measures the headline and nothing else: set-up, the clock-settle launches and W warm-up steps, K timed steps,
+--dump-outputs, the line.  --full measures the rest as well: the headline's cold first launch, the contract read literally
+from an idle chip (both before its timed steps) and board power; every other workload of WORKLOADS; accuracy vs the oracle;
+the end-to-end models; the train step; the CPU baseline.  Their scalars join the line (`literal_protocol_*`, the
+Lab / HSV / RGB-only / 8-bit-content `roofline` scalars, `cpu_baseline`, four accuracy scalars, the train step's three);
+the whole record goes to bench_detail.json (write_detail) and to stderr, never stdout.
 
 --dump-outputs DIR: after the timed steps, what the headline workload's last timed step returned is written as
 DIR/<name>.npy (host_outputs: float32, float64 where the kernel returns float64 or int64; < 64 MB in all, larger
@@ -46,6 +51,11 @@ def disk_mask(B, H, W, device):
     xx = torch.arange(W, device=device, dtype=torch.float32).view(1, W)
     d = ((yy - H / 2) / (H / 2)) ** 2 + ((xx - W / 2) / (W / 2)) ** 2
     return (d < 0.9).view(1, 1, H, W).expand(B, 1, H, W).contiguous()  # ~70 % coverage, bool
+
+
+def make_masks(B, device):
+    return {"disk": disk_mask(B, H_IMG, W_IMG, device),
+            "ones": torch.ones(B, 1, H_IMG, W_IMG, dtype=torch.bool, device=device), None: None}
 
 
 def make_inputs(B, device, seed, n_sets=2):
@@ -612,8 +622,6 @@ def load_traffic(kernel_fragment, workload=None):
     return None, None, None
 
 
-# what a scaling run (N > 1) measures beside the headline unless --full is given
-SCALING_RUN_WORKLOADS = ("lab_stage", "rgb_only")
 LINE_BUDGET = 4096  # bytes: the driver keeps an 8 KB tail of stdout; r04's 20.9 KB line could not be read back
 
 
@@ -639,12 +647,12 @@ def _hbm_view(res):
     return r if r["bound"] == "hbm" else r["secondary"]
 
 
-def make_line(main_res, others, accuracy, cpu, meta, train=None):
+def make_line(main_res, others, accuracy, cpu, meta, train=None, detail=True):
     """The ONE stdout line: the contract's keys, the headline kernel's `roofline` (+ the scalars of the kernels north_star's
     targets name: the fused Lab stage the 70 % figure is stated on, the HSV stage, RGB-only curves = BASELINE configs[1],
     the layer on coherent 8-bit content), `cpu_baseline`, four accuracy scalars and the figure of the contract read
-    literally (no clock-settle launches).  `others` maps workload name -> measure() record.  Nothing here grows with the
-    workload table: that lives in bench_detail.json."""
+    literally (no clock-settle launches), each where measured.  `others` maps workload name -> measure() record.  Nothing
+    here grows with the workload table: that lives in bench_detail.json (`detail`: whether this run writes it)."""
     world, B = meta["n_gpus"], meta["batch_per_gpu"]
     r = main_res["roofline"]
     roof = {"bound": r["bound"], "achieved": r["achieved"], "peak": r["peak"], "unit": r["unit"], "frac": r["frac"],
@@ -691,7 +699,8 @@ def make_line(main_res, others, accuracy, cpu, meta, train=None):
         line["train_step"] = {k: train[k] for k in ("ms_per_step", "images_per_s", "curve_layer_share_of_step") if k in train}
         if meta.get("gpus_visible", world) < world:
             line["rehearsal"] = f"{world} ranks share {meta['gpus_visible']} GPU(s) over {meta.get('backend')}: not a scaling measurement"
-    line["detail"] = "bench_detail.json (also on stderr)"
+    if detail:
+        line["detail"] = "bench_detail.json (also on stderr)"
     return line
 
 
@@ -733,8 +742,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--workload", default="layer", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-extras", action="store_true", help="skip other_workloads / cpu_baseline / accuracy")
-    ap.add_argument("--full", action="store_true", help="N > 1: measure the whole workload table, as N = 1 does")
+    ap.add_argument("--full", action="store_true", help="beside the headline, measure the cold first launch, the literal "
+                    "protocol, board power, every other workload, accuracy vs the oracle, the end-to-end models, the train "
+                    "step and the CPU baseline, and write bench_detail.json")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline workload's last timed step returned "
                     "to DIR/<name>.npy (float32/float64, < 64 MB in all; rank 0)")
     args = ap.parse_args()
@@ -783,8 +793,7 @@ def main():
 
     B = args.batch
     sets = make_inputs(B, device, seed=rank)  # each rank synthesises ITS shard of the global batch
-    masks = {"disk": disk_mask(B, H_IMG, W_IMG, device),
-             "ones": torch.ones(B, 1, H_IMG, W_IMG, dtype=torch.bool, device=device), None: None}
+    masks = make_masks(B, device)
 
     dumped = {}
 
@@ -794,14 +803,14 @@ def main():
         step = make_step(name, ops, masks, sets)
         npx_rank = workload_pixels(name, B)
         cold_us = cold_first_launch_us(step, sets, device) if cold else None
-        cold_ms = cold_start_run(step, sets, steps, warmup, device) if cold and not args.no_extras else None
+        cold_ms = cold_start_run(step, sets, steps, warmup, device) if cold else None
         last = [] if dump else None
         wall, dev_ms, dev_ms_min = timed_run(step, sets, steps, warmup, dist, device, last=last)
         if dump:  # to the host now: nothing after the timed region may touch what the step returned
             dumped.update(host_outputs(last[0]))
             del last[:]
         power = None
-        if cold and rank == 0 and not args.no_extras:
+        if cold and rank == 0:
             # the hwmon power reading is a slow average (the ~0.3 s timed region is too short for it): the same step
             # is kept running for 3 more seconds, outside the timing, and the second half of the samples is reported
             with BoardPower(device.index or 0) as bp:
@@ -850,25 +859,22 @@ def main():
             res["power"] = power
         return res
 
-    main_res = measure(args.workload, args.steps, args.warmup, cold=True, dump=args.dump_outputs is not None and rank == 0)
+    main_res = measure(args.workload, args.steps, args.warmup, cold=args.full,
+                       dump=args.dump_outputs is not None and rank == 0)
     if dumped:
         write_outputs(args.dump_outputs, dumped)
-    # N = 1: the whole table.  N > 1 (the scaling run): the headline, the two kernels north_star's targets name and the
-    # data-parallel train step -- the time goes to the scaling number; --full restores the table
-    names = [n for n in WORKLOADS if n != args.workload]
-    if world > 1 and not args.full:
-        names = [n for n in SCALING_RUN_WORKLOADS if n != args.workload]
+    # a plain run ends here but for the line; --full measures the whole table
+    names = [n for n in WORKLOADS if n != args.workload] if args.full else []
     others = {}
-    if not args.no_extras:
-        for name in names:
-            # >= 200 timed launches (>= 40 ms) each: the Lab-stage figure the 70 % target is quoted on rides here
-            others[name] = measure(name, max(200, args.steps // 2), max(3, args.warmup // 2))
+    for name in names:
+        # >= 200 timed launches (>= 40 ms) each: the Lab-stage figure the 70 % target is quoted on rides here
+        others[name] = measure(name, max(200, args.steps // 2), max(3, args.warmup // 2))
 
     def run_train_step():
         # Every rank takes part (DDP's all-reduce), so a failure on ONE rank must not leave the others waiting in a
         # collective: the ranks first agree (one MIN all-reduce) that each of them could build the model and run a step
         # alone; only then does the data-parallel measurement start.  Context only, never at the expense of the line.
-        if args.no_extras or os.environ.get("CURL_BENCH_TRAIN_STEP", "1") == "0":
+        if not args.full or os.environ.get("CURL_BENCH_TRAIN_STEP", "1") == "0":
             return None
         train = None
         try:
@@ -889,27 +895,27 @@ def main():
             train = {"error": repr(e)}
         return train
 
-    # N = 1: the train step is measured first and its three scalars ride in the line.  N > 1: THE LINE GOES OUT FIRST -- the
-    # data-parallel train step is the one part of this program that needs every rank to answer a collective, and a rank
-    # lost in it must not cost the scaling run its headline; its record goes to bench_detail.json / stderr afterwards.
+    # --full, N = 1: the train step is measured first and its three scalars ride in the line.  N > 1: THE LINE GOES OUT
+    # FIRST -- the data-parallel train step is the one part of this program that needs every rank to answer a collective, and
+    # a rank lost in it must not cost the scaling run its headline; its record goes to bench_detail.json / stderr afterwards.
     train = run_train_step() if world == 1 else None
     meta = {"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "batch_per_gpu": B, "backend": backend,
             "ranks_seen": world if dist is None else dist.get_world_size(), "gpus_visible": n_dev}
     detail = None
     if rank == 0:
         accuracy = end = cpu = None
-        if not args.no_extras:
+        if args.full:
             accuracy = accuracy_vs_oracle(ops, device)
-            if world == 1 or args.full:
-                try:
-                    end = end_to_end(ops, device, sets, masks)
-                except Exception as e:  # context only: never at the expense of the line
-                    end = {"error": repr(e)}
+            try:
+                end = end_to_end(ops, device, sets, masks)
+            except Exception as e:  # context only: never at the expense of the line
+                end = {"error": repr(e)}
             # rank 0's host cores, after every timed region (the other ranks wait at the next collective)
             cpu = cpu_baseline()
-        line = make_line(main_res, others, accuracy, cpu, meta, train)
-        detail = {"line": line, "headline": main_res, "other_workloads": others, "accuracy": accuracy,
-                  "end_to_end": end, "train_step": train, "cpu_baseline": cpu, "meta": meta}
+        line = make_line(main_res, others, accuracy, cpu, meta, train, detail=args.full)
+        if args.full:
+            detail = {"line": line, "headline": main_res, "other_workloads": others, "accuracy": accuracy,
+                      "end_to_end": end, "train_step": train, "cpu_baseline": cpu, "meta": meta}
         print(dump_line(line))
         sys.stdout.flush()
     if world > 1:

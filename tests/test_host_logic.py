@@ -448,12 +448,92 @@ def test_bench_line_is_compact_strict_json_with_the_contract_keys(world):
     assert json.loads(bare)["roofline"]["frac"] == r["frac"]
 
 
-def test_scaling_run_measures_the_targets_only():
+def test_plain_run_measures_the_headline_only(monkeypatch, capsys):
+    """A plain `bench.py` run times the headline workload and prints the line, nothing else: no cold-start, literal-protocol
+    or power runs, no other workload, no accuracy, end-to-end, train-step or CPU measurement, no bench_detail.json.
+    --full runs each of them once (the cold runs before the headline's timed steps) and puts their scalars in the line."""
+    import itertools
+    import json
     import os
     import sys
+    import types
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
-    assert set(bench.SCALING_RUN_WORKLOADS) == {"lab_stage", "rgb_only"} and set(bench.SCALING_RUN_WORKLOADS) < set(bench.WORKLOADS)
+    from curl_amd import _lib
+    calls = []
+
+    def fake_step(name, ops_, masks, sets=None):
+        step = lambda s: None  # noqa: E731
+        step.workload = name
+        return step
+
+    def fake_timed(step, sets, steps, warmup, dist, device, last=None):
+        calls.append(("timed", step.workload, steps, warmup))
+        return 0.2e-3 * steps, 0.2, 0.2
+
+    def stub(name, ret):
+        def f(*a, **k):
+            calls.append(name)
+            return ret
+        return f
+
+    class FakePower:
+        def __init__(self, index):
+            self.samples = []
+
+        def __enter__(self):
+            calls.append("power")
+            return self
+
+        def __exit__(self, *exc):
+            pass
+
+        def summary(self):
+            return None
+
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("CURL_BENCH_TRAIN_STEP", "1")
+    for k, v in (("is_available", lambda: True), ("device_count", lambda: 1), ("set_device", lambda d: None),
+                 ("synchronize", lambda d=None: None)):
+        monkeypatch.setattr(bench.torch.cuda, k, v)
+    monkeypatch.setattr(_lib, "load", lambda: None)
+    monkeypatch.setattr(bench, "make_inputs", lambda B, device, seed: [(None,) * 6] * 2)
+    monkeypatch.setattr(bench, "make_masks", lambda B, device: {"disk": None, "ones": None, None: None})
+    monkeypatch.setattr(bench, "make_step", fake_step)
+    monkeypatch.setattr(bench, "timed_run", fake_timed)
+    monkeypatch.setattr(bench, "BoardPower", FakePower)
+    monkeypatch.setattr(bench, "time", types.SimpleNamespace(perf_counter=itertools.count().__next__, sleep=lambda s: None))
+    extras = {"cold_first_launch_us": 431.0, "cold_start_run": 0.25, "accuracy_vs_oracle": {"max_abs_err": 2e-5},
+              "end_to_end": {}, "cpu_baseline": {"value": 2.5, "unit": "Mpix/s"}, "train_step_preflight": None,
+              "train_step_record": {"ms_per_step": 42.0, "images_per_s": 760.0, "curve_layer_share_of_step": 1e-3},
+              "write_detail": None}
+    for name, ret in extras.items():
+        monkeypatch.setattr(bench, name, stub(name, ret))
+    argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+
+    monkeypatch.setattr(sys, "argv", argv)
+    bench.main()
+    line = json.loads(capsys.readouterr().out)
+    assert calls == [("timed", "layer", 20, 5)]
+    assert line["metric"].startswith("Mpix/s through fused curve-apply") and line["unit"] == "Mpix/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["ms_per_step"] - 0.2) < 1e-9 and abs(line["value"] - 48e6 / 0.2e-3 / 1e6) < 1
+    assert line["roofline"]["bound"] == "hbm" and line["literal_protocol_ms_per_step"] is None
+    for k in ("cpu_baseline", "accuracy", "train_step", "detail", "lab_stage_us"):
+        assert k not in line and k not in line["roofline"], k
+
+    calls.clear()
+    monkeypatch.setattr(sys, "argv", argv + ["--full"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out)
+    assert [c[1] for c in calls if isinstance(c, tuple)] == list(bench.WORKLOADS)  # the headline ("layer") first
+    for name in list(extras) + ["power"]:
+        assert calls.count(name) == 1, name
+    assert calls.index("cold_start_run") < calls.index(("timed", "layer", 20, 5)) < calls.index("power")
+    assert line["literal_protocol_ms_per_step"] == 0.25 and line["roofline"]["lab_stage_us"] > 0
+    assert line["cpu_baseline"]["value"] == 2.5 and line["accuracy"]["max_abs_err"] == 2e-5
+    assert line["train_step"]["ms_per_step"] == 42.0 and line["detail"].startswith("bench_detail.json")
 
 
 def test_bench_dump_outputs_budget_and_sample(tmp_path):

@@ -90,7 +90,7 @@ def main(path):
     detail = json.load(open(path))
     line = detail["line"]
     src = os.path.relpath(os.path.abspath(path), ROOT)
-    head = (f"Numbers: `{src}` (`python bench.py --steps {line['steps']} --warmup {line['warmup']}`, one MI355X, HIP events on the "
+    head = (f"Numbers: `{src}` (`python bench.py --full --steps {line['steps']} --warmup {line['warmup']}`, one MI355X, HIP events on the "
             f"launch stream, per call incl. every launch of the call) and the committed counter passes `profiles/traffic_r0*.json`; "
             f"batch 32 × 1500×1000 unless the row says otherwise.  Headline: **{line['value']:.0f} Mpix/s**, "
             f"{line['ms_per_step']:.4f} ms per step (wall), kernel-side {line['roofline']['frac']:.3f} of the HBM peak; the contract read "

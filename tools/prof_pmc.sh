@@ -5,4 +5,4 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/pmc_${TAG}_${W}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -- python3 $R/bench.py --workload $W --steps 60 --warmup 60 --no-extras > $OUT/run.json 2> $OUT/run.err
+timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -- python3 $R/bench.py --workload $W --steps 60 --warmup 60 > $OUT/run.json 2> $OUT/run.err
