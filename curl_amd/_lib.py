@@ -54,6 +54,9 @@ SIGNATURES = {
     "curl_layer_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "curl_layer_bwd_f32": (_i, [_c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                 _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _i, _i, _u, _c_f]),
+    "curl_layer_pwl_bwd_scratch_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "curl_layer_pwl_bwd_f32": (_i, [_c_f, _c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                    _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _i, _i, _u, _c_f]),
     # backward of the stand-alone curve ops, converters and fused stages
     "curl_adjust_rgb_bwd_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u, _c_f]),
     "curl_adjust_lab_bwd_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _i, _i, _i, _i, _u, _c_f]),

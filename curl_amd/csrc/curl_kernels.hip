@@ -201,6 +201,7 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/ops.inc"
 #include "kernels/chain.inc"
 #include "kernels/layer_bwd.inc"
+#include "kernels/layer_pwl_bwd.inc"
 #include "kernels/stage_bwd.inc"
 #include "kernels/psnr.inc"
 #include "kernels/msssim.inc"

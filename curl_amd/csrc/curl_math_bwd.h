@@ -525,6 +525,148 @@ CURL_HD Px hsv_stage_bwd(Px in, float m, const Affine* k, Px gout, float* P, flo
   return rgb2hsv_pull(t_hsv, g);
 }
 
+// ---------------------------------------------------------------- the paper's piecewise-linear curves (CURL_F_PWL)
+// The layer of OpLayerTab<0> (kernels/ops.inc), curve by curve: scale = C_i + slope_i f, s = S x, i = clamp(floor(s), 0, K-2),
+// f = clamp01(s - i) (curl_math.h scale_pwl_pairs), the {C_i, slope_i} pairs read from a table.  The same function is
+// C_0 + sum_j slope_j clamp01(s - j), so with G = d loss / d scale at a pixel
+//   d loss / d C_0 += G,   d loss / d slope_j += G clamp01(s - j)   (j = 0 .. K-2),
+// a K-wide sum per curve: the pullback hands every curve's (s, G) to the caller's accumulator, `acc(curve, s, G)`, which does
+// the summing (kernels/layer_pwl_bwd.inc: in registers, then wave sums; the host twin: in float64).  d scale / d x = S slope_i
+// where 0 <= s - i <= 1 (both ends: torch.clamp's gradient convention), else 0 -- pixels on a knot take the right-hand
+// segment's slope, the derivative of the forward as it is evaluated.
+struct PwlCurveT {
+  float x, s, ds;  // the input, S x, d pre / d x = scale + x d scale / d x
+  lmask pass;      // 0 <= pre <= 1
+};
+// scale at x and d scale / d x (0 outside the segment's closed interval)
+CURL_HD float pwl_scale_d(float x, const float* tab, int K, float& s, float& dsc) {
+  const float S = (float)(K - 1);
+  s = S * x;
+  const float fi = clampf(floorf(s), 0.0f, (float)(K - 2));
+  const int i = (int)fi;
+  lmask in_seg;
+  const float f = clamp_gate(s - fi, 0.0f, 1.0f, in_seg);
+  const float sl = tab[2 * i + 1];
+  dsc = lm_keep(in_seg, S * sl);
+  return fmaf(sl, f, tab[2 * i]);
+}
+CURL_HD float pwl_self_t(float x, const float* tab, int K, PwlCurveT& t) {
+  float dsc;
+  const float sc = pwl_scale_d(x, tab, K, t.s, dsc);
+  t.x = x;
+  t.ds = fmaf(x, dsc, sc);
+  return clamp_gate(x * sc, 0.0f, 1.0f, t.pass);
+}
+template <int C, class Acc>
+CURL_HD float pwl_self_pull(const PwlCurveT& t, float gy, Acc& acc) {
+  const float g_pre = lm_keep(t.pass, gy);
+  acc(C, t.s, g_pre * t.x);
+  return g_pre * t.ds;
+}
+// y = clamp01(xo scale(xi)): adjust_hsv's H -> S curve on the adjusted hue
+struct PwlCrossT {
+  float xo, s, sc, dsc;
+  lmask pass;
+};
+CURL_HD float pwl_cross_t(float xo, float xi, const float* tab, int K, PwlCrossT& t) {
+  t.sc = pwl_scale_d(xi, tab, K, t.s, t.dsc);
+  t.xo = xo;
+  return clamp_gate(xo * t.sc, 0.0f, 1.0f, t.pass);
+}
+template <int C, class Acc>
+CURL_HD void pwl_cross_pull(const PwlCrossT& t, float gy, float& g_xo, float& g_xi, Acc& acc) {
+  const float g_pre = lm_keep(t.pass, gy);
+  const float G = g_pre * t.xo;
+  g_xo = g_pre * t.sc;
+  g_xi = fmaf(G, t.dsc, g_xi);
+  acc(C, t.s, G);
+}
+// adjust_lab / adjust_rgb: channel 0 meets its curve unclamped, channels 1 and 2 clamped first (OpLayerTab::adjust3_pwl)
+struct PwlAdjust3T {
+  PwlCurveT c[3];
+  lmask in1, in2;
+};
+CURL_HD Px pwl_adjust3_t(Px p, const float* T, int K, PwlAdjust3T& t) {
+  Px o;
+  o.c0 = pwl_self_t(p.c0, T, K, t.c[0]);
+  o.c1 = pwl_self_t(clamp_gate(p.c1, 0.0f, 1.0f, t.in1), T + 2 * K, K, t.c[1]);
+  o.c2 = pwl_self_t(clamp_gate(p.c2, 0.0f, 1.0f, t.in2), T + 4 * K, K, t.c[2]);
+  return o;
+}
+template <int C0, class Acc>
+CURL_HD Px pwl_adjust3_pull(const PwlAdjust3T& t, Px g, Acc& acc) {
+  Px gi;
+  gi.c0 = pwl_self_pull<C0>(t.c[0], g.c0, acc);
+  gi.c1 = lm_keep(t.in1, pwl_self_pull<C0 + 1>(t.c[1], g.c1, acc));
+  gi.c2 = lm_keep(t.in2, pwl_self_pull<C0 + 2>(t.c[2], g.c2, acc));
+  return gi;
+}
+// adjust_hsv: H -> H, then H -> S on the adjusted hue, S -> S, V -> V.  UNIT: s and v arrive in [0,1] (adjust_hsv4_t)
+struct PwlAdjustHsvT {
+  PwlCurveT hh, ss, vv;
+  PwlCrossT hs;
+  lmask in1, in2;
+};
+template <bool UNIT>
+CURL_HD Px pwl_adjust_hsv_t(Px p, const float* T, int K, PwlAdjustHsvT& t) {
+  const float h1 = pwl_self_t(p.c0, T, K, t.hh);
+  const float sc = UNIT ? p.c1 : clamp_gate(p.c1, 0.0f, 1.0f, t.in1), vc = UNIT ? p.c2 : clamp_gate(p.c2, 0.0f, 1.0f, t.in2);
+  const float s1 = pwl_cross_t(sc, h1, T + 2 * K, K, t.hs);
+  Px o;
+  o.c0 = h1;
+  o.c1 = pwl_self_t(s1, T + 4 * K, K, t.ss);
+  o.c2 = pwl_self_t(vc, T + 6 * K, K, t.vv);
+  return o;
+}
+template <bool UNIT, class Acc>
+CURL_HD Px pwl_adjust_hsv_pull(const PwlAdjustHsvT& t, Px g, Acc& acc) {
+  const float g_vc = pwl_self_pull<9>(t.vv, g.c2, acc);
+  const float g_s1 = pwl_self_pull<8>(t.ss, g.c1, acc);
+  float g_sc, g_h1 = g.c0;
+  pwl_cross_pull<7>(t.hs, g_s1, g_sc, g_h1, acc);
+  Px gi;
+  gi.c0 = pwl_self_pull<6>(t.hh, g_h1, acc);
+  gi.c1 = UNIT ? g_sc : lm_keep(t.in1, g_sc);
+  gi.c2 = UNIT ? g_vc : lm_keep(t.in2, g_vc);
+  return gi;
+}
+// The whole layer with PWL curves (OpLayerTab<0>::apply_n's order).  T: the image's table, {knot, slope} pairs of the ten
+// curves back to back (3 x Kl, 3 x Kr, 4 x Kh: the layout the forward stages in LDS).  Curves are numbered as in
+// curl_layer_bwd (0-2 Lab, 3-5 RGB, 6-9 HSV).  BINARY / NEED_GIN as there.  `y` receives the recomputed forward output (the
+// host twin checks it; the kernels ignore it).  Returns d loss / d in.
+template <bool BINARY, bool NEED_GIN, class Acc>
+CURL_HD Px curl_layer_pwl_bwd(Px in, float m, const float* T, int Kl, int Kr, int Kh, Px gout, Acc& acc, Px& y) {
+  const float *Tl = T, *Tr = T + 6 * Kl, *Th = Tr + 6 * Kr;
+  Rgb2LabT t_lab;
+  PwlAdjust3T t_al, t_ar;
+  Lab2RgbT t_rgb;
+  Rgb2HsvT t_hsv;
+  PwlAdjustHsvT t_ah;
+  Hsv2RgbT t_res;
+  Px x = pwl_adjust3_t(rgb2lab_t(in, t_lab), Tl, Kl, t_al);
+  if (!BINARY) x = Px{x.c0 * m, x.c1 * m, x.c2 * m};  // model.py:154
+  x = pwl_adjust3_t(lab2rgb_t(x, t_rgb), Tr, Kr, t_ar);
+  if (!BINARY) x = Px{x.c0 * m, x.c1 * m, x.c2 * m};  // model.py:160
+  x = pwl_adjust_hsv_t<BINARY>(rgb2hsv_t(x, t_hsv), Th, Kh, t_ah);
+  if (!BINARY) x = Px{x.c0 * m, x.c1 * m, x.c2 * m};  // model.py:166
+  const Px res = hsv2rgb_t<BINARY>(x, t_res);
+  lmask o0, o1, o2;  // out = clamp01(in + res) * m   (model.py:170)
+  y.c0 = clamp_gate(in.c0 + res.c0, 0.0f, 1.0f, o0) * m;
+  y.c1 = clamp_gate(in.c1 + res.c1, 0.0f, 1.0f, o1) * m;
+  y.c2 = clamp_gate(in.c2 + res.c2, 0.0f, 1.0f, o2) * m;
+  const Px g_pre{lm_keep(o0, gout.c0 * m), lm_keep(o1, gout.c1 * m), lm_keep(o2, gout.c2 * m)};
+  Px g = hsv2rgb_pull<BINARY>(t_res, g_pre);
+  if (!BINARY) g = Px{g.c0 * m, g.c1 * m, g.c2 * m};
+  g = rgb2hsv_pull(t_hsv, pwl_adjust_hsv_pull<BINARY>(t_ah, g, acc));
+  if (!BINARY) g = Px{g.c0 * m, g.c1 * m, g.c2 * m};
+  g = lab2rgb_pull(t_rgb, pwl_adjust3_pull<3>(t_ar, g, acc));
+  if (!BINARY) g = Px{g.c0 * m, g.c1 * m, g.c2 * m};
+  g = pwl_adjust3_pull<0>(t_al, g, acc);
+  if constexpr (!NEED_GIN) return g;  // (not d loss / d in: the caller ignores it)
+  g = rgb2lab_pull(t_lab, g);
+  return Px{g.c0 + g_pre.c0, g.c1 + g_pre.c1, g.c2 + g_pre.c2};
+}
+
 // ---- per image: (P, Q) of one curve + d loss / d reg  ->  gradient of that curve's RAW knots (pre-exp).
 // C = exp(raw) (already computed); scale = C0 + sum_{j<=K-3} slope_j (S x - j); reg = sum_j (slope_{j+1}-slope_j)^2.
 // Everything in float64: K is tiny and this runs once per curve per image.
@@ -568,6 +710,21 @@ CURL_HD float knot_bwd5(const float (&c)[5], int K, double P, double Q, double g
 }
 CURL_HD void knots_bwd(const float* C, int K, double P, double Q, double g_reg, float* g_raw) {
   for (int kk = 0; kk < K; ++kk) g_raw[kk] = knot_bwd(C, K, P, Q, g_reg, kk);
+}
+// The same for a PWL curve: T[0] = sum G (d loss / d C_0 from the pixels), T[1 + j] = sum G clamp01(s - j) = d loss / d slope_j
+// from the pixels (j = 0 .. K-2); the regulariser's terms are knot_bwd's.
+CURL_HD float knot_bwd_pwl(const float* C, int K, const double* T, double g_reg, int kk) {
+  auto dslope = [&](int j) -> double {
+    if (j < 0 || j > K - 2) return 0.0;
+    double v = T[1 + j];  // pixels
+    auto sl = [&](int i) { return (double)(C[i + 1] - C[i]); };
+    if (j >= 1) v += g_reg * 2.0 * (sl(j) - sl(j - 1));
+    if (j + 1 <= K - 2) v -= g_reg * 2.0 * (sl(j + 1) - sl(j));
+    return v;
+  };
+  double gC = dslope(kk - 1) - dslope(kk);
+  if (kk == 0) gC += T[0];  // the C_0 term of the scale
+  return (float)(gC * (double)C[kk]);  // d exp(raw) = C
 }
 
 }  // namespace curlm

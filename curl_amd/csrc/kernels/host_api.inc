@@ -536,13 +536,14 @@ static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, con
 // (the autograd nodes keep it), and the prep launch and its kernel boundary go (a fifth of a training-crop-batch backward).
 static int bwd_prologue(const float* img, const float* grad_out, const void* mask, int mask_kind, unsigned flags,
                         const void* workspace, size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int B, int H,
-                        int W, int n_knots, const PrepArgs& prep, hipStream_t s) {
+                        int W, int n_knots, const PrepArgs& prep, hipStream_t s, size_t scratch_need = 0,
+                        const char* scratch_msg = "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes") {
   if (int rc = check_img(img, grad_out, B, H, W)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;  // (+ CURL_F_MASK_FIRST, CURL_F_TUNE_PREP: allowed everywhere)
   if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
-  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_layer_bwd_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes");
+  if (!scratch_need) scratch_need = curl_layer_bwd_scratch_bytes(B, H, W);
+  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < scratch_need) return fail(CURL_E_WORKSPACE, scratch_msg);
   return (flags & CURL_F_WS_READY) ? 0 : launch_prep(prep, B, s);
 }
 
@@ -635,7 +636,8 @@ extern "C" {
 // 0.1.6: same entry points; curl_layer_bwd_f32 with grad_img = NULL runs its own kernel; gradients at black pixels, at
 //        prediction == target (CURLLoss) and the PSNR of equal images under a float mask follow the reference (DESIGN.md 3e.8-9)
 // 0.1.9: backward entry points of the stand-alone curve ops, converters and fused stages (curl_*_bwd_f32)
-int curl_version(void) { return 109; }
+// 0.1.10: curl_layer_pwl_bwd_f32, the fused layer's backward with the paper's piecewise-linear curves (CURL_F_PWL)
+int curl_version(void) { return 110; }
 
 const char* curl_last_error(void) { return g_err; }
 
@@ -899,6 +901,75 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
   hipLaunchKernelGGL(knots_bwd_kernel, dim3(B), dim3(KNOTS_BWD_THREADS), 0, s, kb);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "knots_bwd_kernel");
+  return 0;
+}
+
+size_t curl_layer_pwl_bwd_scratch_bytes(int B, int H, int W, int Kl, int Kr, int Kh) {
+  if (B <= 0 || H <= 0 || W <= 0 || Kl < 2 || Kr < 2 || Kh < 2 || Kl > CURL_MAX_KNOTS || Kr > CURL_MAX_KNOTS || Kh > CURL_MAX_KNOTS)
+    return 0;
+  size_t HW = (size_t)H * W;
+  size_t blocks = (HW + 255) / 256;  // upper bound: the scalar path, one pixel per lane
+  return (size_t)B * blocks * (size_t)layer_n_knots(Kl, Kr, Kh) * sizeof(float);
+}
+
+// The fused layer's backward with the paper's curves: curl_layer_bwd_f32's arguments and checks, one row of n_knots block
+// partials per workgroup (layer_pwl_bwd_kernel), then one workgroup per curve and image (layer_pwl_knots_bwd_kernel).
+int curl_layer_pwl_bwd_f32(const float* img, const void* mask, int mask_kind, const float* rawL, const float* rawR,
+                           const float* rawH, const float* grad_out, const float* grad_reg, float* grad_img,
+                           float* grad_rawL, float* grad_rawR, float* grad_rawH, void* workspace, size_t workspace_bytes,
+                           void* scratch, size_t scratch_bytes, int B, int H, int W, int Kl, int Kr, int Kh, unsigned flags,
+                           curl_stream_t stream) {
+  g_err[0] = 0;
+  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, false)) return rc;
+  if (!grad_rawL || !grad_rawR || !grad_rawH) return fail(CURL_E_NULL, "grad_rawL/R/H must all be non-NULL");
+  if (flags & ~(CURL_F_WS_READY | CURL_F_MASK_FIRST)) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point");
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  const int n_knots = layer_n_knots(Kl, Kr, Kh);
+  const unsigned stride = ws_stride(n_knots);
+  const size_t need = (B > 0 && H > 0 && W > 0) ? curl_layer_pwl_bwd_scratch_bytes(B, H, W, Kl, Kr, Kh) : 0;
+  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
+                            n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s, need,
+                            "scratch missing, misaligned or smaller than curl_layer_pwl_bwd_scratch_bytes"))
+    return rc;
+  const size_t HW = (size_t)H * W;
+  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
+  PwlBwdArgs a;
+  a.in = img;
+  a.gout = grad_out;
+  a.gin = grad_img;
+  a.mask = mask_kind ? mask : nullptr;
+  a.ws = ws;
+  a.partial = (float*)scratch;
+  a.ws_stride = stride;
+  a.n = (unsigned)(HW / (aligned ? 4 : 1));
+  a.blocks_per_image = (a.n + 255u) / 256u;
+  a.kl = Kl, a.kr = Kr, a.kh = Kh;
+  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
+  a.stamp = ws_stamp((unsigned)n_knots, stride);
+  if ((uint64_t)a.blocks_per_image * (uint64_t)B > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
+  const dim3 grid(a.blocks_per_image, (unsigned)B), block(256);
+  const size_t lds = pwl_bwd_lds_bytes(Kl, Kr, Kh);
+#define LAUNCH_PWL_BWD(V, M)                                                                          \
+  do {                                                                                                \
+    if (grad_img) hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, true>), grid, block, lds, s, a);     \
+    else hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, false>), grid, block, lds, s, a);             \
+  } while (0)
+  DISPATCH_VEC_MASK(LAUNCH_PWL_BWD, aligned, mask_kind);
+#undef LAUNCH_PWL_BWD
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "layer_pwl_bwd_kernel");
+  PwlKnotsBwdArgs kb;
+  kb.ws = ws;
+  kb.partial = (const float*)scratch;
+  kb.greg = grad_reg;
+  kb.graw[0] = grad_rawL, kb.graw[1] = grad_rawR, kb.graw[2] = grad_rawH;
+  kb.K[0] = Kl, kb.K[1] = Kr, kb.K[2] = Kh;
+  kb.ws_stride = stride;
+  kb.blocks_per_image = a.blocks_per_image;
+  hipLaunchKernelGGL(layer_pwl_knots_bwd_kernel, dim3(MAX_CURVES, (unsigned)B), dim3(PWL_KNOTS_THREADS), 0, s, kb);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "layer_pwl_knots_bwd_kernel");
   return 0;
 }
 

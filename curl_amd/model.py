@@ -11,7 +11,8 @@ from . import colors, metric, ops
 
 
 class _CurlLayerFn(torch.autograd.Function):
-    """Autograd node around the fused forward/backward kernels."""
+    """Autograd node around the fused forward/backward kernels (flags: F_MASK_FIRST, and F_PWL for the paper's curves --
+    ops.curl_layer_backward takes the same flags to the matching backward)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)  # under autocast: float32 in, autocast off
@@ -36,7 +37,8 @@ class _CurlLayerFn(torch.autograd.Function):
 class CURLLayer(nn.Module):
     """model.py:121-176.  Same constructor arguments, same forward signature and returns.
     `paper_pwl=True` (not in the reference) evaluates the curves as the paper's clamped piecewise-linear
-    interpolation of the knots (CURL_F_PWL: knots in LDS) instead of the reference's affine form; inference only.
+    interpolation of the knots (CURL_F_PWL: knots in LDS) instead of the reference's affine form; under grad it trains
+    through its own backward kernels (curl_layer_pwl_bwd_f32; knot counts that torch.chunk splits evenly only).
     `foreground_masks=True` (not in the reference either) tells the kernel that the bool / uint8 masks it will see have
     sizeable empty regions (data.py:186-190: segmentation masks): wavefronts test their mask bytes before asking for their
     pixels and never read fully masked-out tiles (CURL_F_MASK_FIRST: -7 % at 70 % coverage, -25 % at 40 %, +0.9 % on an
@@ -64,13 +66,10 @@ class CURLLayer(nn.Module):
         R = R[:, :self.num_rgb_points]  # model.py:159
         H = H[:, :self.num_hsv_points]  # model.py:165
         needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (img, L, R, H))
-        if self.paper_pwl:
-            if needs_grad:
-                raise NotImplementedError("curl_amd: paper_pwl has no backward (the reference's curves are the affine form)")
-            return ops.curl_layer_forward(img, mask, L, R, H, flags=ops.F_PWL | self.flags)
+        flags = ops.F_PWL | self.flags if self.paper_pwl else self.flags
         if needs_grad:
-            return _CurlLayerFn.apply(img, mask, L, R, H, self.flags)
-        return ops.curl_layer_forward(img, mask, L, R, H, flags=self.flags)
+            return _CurlLayerFn.apply(img, mask, L, R, H, flags)
+        return ops.curl_layer_forward(img, mask, L, R, H, flags=flags)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -248,10 +247,10 @@ class GCURLNet(nn.Module):
     (num_lab_points + num_rgb_points + num_hsv_points) and the backbone is injectable.
     `encoder_size` (optional): the encoder sees the image resized to this square while the curves are
     applied at full resolution -- the low-res-encode / full-res-apply shape of infer.py:32-44.
-    `foreground_masks`: see CURLLayer."""
+    `foreground_masks`, `paper_pwl`: see CURLLayer (the fused layer-plus-loss forward, `target=`, has no PWL form)."""
 
     def __init__(self, num_lab_points=48, num_rgb_points=48, num_hsv_points=64, backbone=None, encoder_size=None,
-                 foreground_masks=False):
+                 foreground_masks=False, paper_pwl=False):
         super().__init__()
         self.num_lab_points = num_lab_points
         self.num_rgb_points = num_rgb_points
@@ -266,7 +265,8 @@ class GCURLNet(nn.Module):
             backbone.classifier = nn.Sequential(nn.Linear(backbone.classifier.in_features, n_out))  # model.py:190-192
         self.backbone = backbone
         self.encoder_size = encoder_size
-        self.curllayer = CURLLayer(num_lab_points, num_rgb_points, num_hsv_points, foreground_masks=foreground_masks)
+        self.curllayer = CURLLayer(num_lab_points, num_rgb_points, num_hsv_points, paper_pwl=paper_pwl,
+                                   foreground_masks=foreground_masks)
 
     def predict_knots(self, img):
         x = img
@@ -285,7 +285,10 @@ class GCURLNet(nn.Module):
             curves[:, self.curve_break_1:self.curve_break_2], \
             curves[:, self.curve_break_2:]
         if target is not None:
-            lay = self.curllayer  # (its foreground_masks / paper_pwl options are the stand-alone layer's: not taken here)
+            lay = self.curllayer  # (its foreground_masks option is the stand-alone layer's: not taken here)
+            if lay.paper_pwl:
+                raise ValueError("curl_amd: the fused layer-plus-loss forward (target=) has the reference's affine curves "
+                                 "only; with paper_pwl call the model without target and apply the criterion to its output")
             L, R, H = L[:, :lay.num_lab_points], R[:, :lay.num_rgb_points], H[:, :lay.num_hsv_points]  # model.py:153,159,165
             out, reg, rgb, cosine, lab, hsv, Lp, Lt = _LayerLossFn.apply(img, mask, L, R, H, target)
             ssim = (1.0 - criterion.msssim_layer(Lp, Lt)).mean() if criterion.msssim_layer is not None else 0.0

@@ -494,10 +494,11 @@ def _grad_reg32(grad_reg, B):
     return grad_reg
 
 
-def _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags, ws_source):
+def _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags, ws_source, sbytes=None):
     """What the layer and the curve backwards share: grad_reg as float32 [B] (or None), the knot workspace -- the caller's
     (CURL_F_WS_READY: `ws_source` filled it for the same knots, the entry point skips its knot prep) or a fresh one -- and
-    the block-partials scratch.  -> (grad_reg, ws, nbytes, bflags, scratch, sbytes)"""
+    the block-partials scratch (sbytes: its size, curl_layer_bwd_scratch_bytes by default).
+    -> (grad_reg, ws, nbytes, bflags, scratch, sbytes)"""
     B, _, H, W = img.shape
     grad_reg = _grad_reg32(grad_reg, B)
     ws, nbytes = _workspace(B, n_knots, img.device)
@@ -506,7 +507,8 @@ def _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags, ws_source):
         if workspace.device != img.device or workspace.dtype != torch.float32 or workspace.numel() * 4 < nbytes:
             raise ValueError(f"workspace is not the tensor {ws_source} for this batch")
         ws, bflags = workspace, bflags | _lib.F_WS_READY
-    sbytes = lib.curl_layer_bwd_scratch_bytes(B, H, W)
+    if sbytes is None:
+        sbytes = lib.curl_layer_bwd_scratch_bytes(B, H, W)
     scratch = torch.empty(sbytes // 4, dtype=torch.float32, device=img.device)
     return grad_reg, ws, nbytes, bflags, scratch, sbytes
 
@@ -515,7 +517,12 @@ def curl_layer_backward(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_i
     """Backward of curl_layer_forward (what autograd would run through model.py:137-176).
     -> (grad_img or None, grad_L, grad_R, grad_H).
     workspace: the tensor curl_layer_forward(..., return_workspace=True) returned for the SAME knots (CURL_F_WS_READY).
-    (Plain calls through the compiled binding, as curl_layer_forward.)"""
+    flags: F_MASK_FIRST (bool / uint8 foreground masks); F_PWL: the backward of curl_layer_forward(..., flags=F_PWL), the
+    paper's piecewise-linear curves (curl_layer_pwl_bwd_f32; even knot splits only).
+    (Plain affine calls through the compiled binding, as curl_layer_forward.)"""
+    if flags & F_PWL:  # (before the binding, which knows the affine entry point only)
+        return _curl_layer_backward_checked(img, mask, L, R, H, grad_out, grad_reg=grad_reg, need_grad_img=need_grad_img,
+                                            workspace=workspace, flags=flags)
     fast = _lib.fast() if type(img) is torch.Tensor else None
     if fast is not None:
         r = fast.layer_bwd(img, mask, L, R, H, grad_out, grad_reg, need_grad_img, workspace, flags & F_MASK_FIRST)
@@ -530,19 +537,31 @@ def curl_layer_backward(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_i
 @_one_device
 def _curl_layer_backward_checked(img, mask, L, R, H, grad_out, grad_reg=None, need_grad_img=True, workspace=None, flags=0):
     lib = _lib.load()
+    pwl = bool(flags & F_PWL)
+    if pwl and _is_empty_image(img):
+        # an empty image owes only the regulariser's share: the same entry point on a 1x1 stand-in with a zero gradient
+        _need_device(img, "img")
+        B = img.shape[0]
+        g_img = torch.empty_like(img) if need_grad_img else None
+        if B == 0:
+            return (g_img,) + tuple(torch.zeros(t.shape, dtype=torch.float32, device=img.device) for t in (L, R, H))
+        z = img.new_zeros((B, 3, 1, 1))
+        return (g_img,) + _curl_layer_backward_checked(z, None, L, R, H, z, grad_reg, False, None, flags)[1:]
     img, grad_out = _image_and_grad(img, grad_out)
     B, _, Hh, W = img.shape
     Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     m, kind = _mask(mask, img)
     g_img = torch.empty_like(img) if need_grad_img else None
     gL, gR, gH = torch.empty_like(Lc), torch.empty_like(Rc), torch.empty_like(Hc)
-    grad_reg, ws, nbytes, bflags, scratch, sbytes = _bwd_setup(lib, img, grad_reg, n_knots, workspace, flags,
-                                                               "curl_layer_forward returned")
-    rc = lib.curl_layer_bwd_f32(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
-                                grad_out.data_ptr(), _ptr(grad_reg), _ptr(g_img), gL.data_ptr(), gR.data_ptr(),
-                                gH.data_ptr(), ws.data_ptr(), nbytes, scratch.data_ptr(), sbytes, B, Hh, W, Kl, Kr, Kh,
-                                bflags, _stream(img))
-    _lib.check(rc, "curl_layer_bwd_f32")
+    grad_reg, ws, nbytes, bflags, scratch, sbytes = _bwd_setup(
+        lib, img, grad_reg, n_knots, workspace, flags, "curl_layer_forward returned",
+        lib.curl_layer_pwl_bwd_scratch_bytes(B, Hh, W, Kl, Kr, Kh) if pwl else None)
+    name = "curl_layer_pwl_bwd_f32" if pwl else "curl_layer_bwd_f32"
+    rc = getattr(lib, name)(img.data_ptr(), _ptr(m), kind, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
+                            grad_out.data_ptr(), _ptr(grad_reg), _ptr(g_img), gL.data_ptr(), gR.data_ptr(),
+                            gH.data_ptr(), ws.data_ptr(), nbytes, scratch.data_ptr(), sbytes, B, Hh, W, Kl, Kr, Kh,
+                            bflags, _stream(img))
+    _lib.check(rc, name)
     return g_img, gL, gR, gH
 
 

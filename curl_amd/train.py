@@ -58,13 +58,14 @@ class SyntheticPairs(Dataset):
         return {"input_img": x, "output_img": y, "mask": mask, "name": f"synthetic_{i:05d}"}
 
 
-def build_net(arch, width, sync_bn, foreground_masks=False):
+def build_net(arch, width, sync_bn, foreground_masks=False, paper_pwl=False):
     if arch == "trispace":  # main.py:221
         net = model.TriSpaceRegNet(polynomial_order=4, spatial=True, use_sync_bn=sync_bn,
                                    backbone=model.CurveEncoder(num_outputs=1, num_features=1024, width=width,
                                                                variant="efficientnetv2_rw_t"))  # model.py:456
     else:
-        net = model.GCURLNet(backbone=model.CurveEncoder(160, width=width), foreground_masks=foreground_masks)
+        net = model.GCURLNet(backbone=model.CurveEncoder(160, width=width), foreground_masks=foreground_masks,
+                             paper_pwl=paper_pwl)
         if sync_bn:
             net = nn.SyncBatchNorm.convert_sync_batchnorm(net)
     return net
@@ -103,6 +104,9 @@ def main(argv=None):
     ap.add_argument("--fused_forward", action="store_true",
                     help="--arch curl: the layer and CURLLoss' pointwise terms as ONE forward kernel (curl_layer_loss_fwd_f32); the "
                          "same loss and gradients as main.py:283-285's two calls")
+    ap.add_argument("--paper_pwl", action="store_true",
+                    help="--arch curl: the paper's clamped piecewise-linear curves instead of the reference's affine form "
+                         "(CURL_F_PWL forward and backward kernels); not with --fused_forward")
     ap.add_argument("--save_images", action="store_true", help="dump validation outputs under --log_dirpath (evaluate.py:49-66)")
     ap.add_argument("--amp", choices=("off", "bf16"), default="off",
                     help="bf16: torch.autocast around the encoder (stock PyTorch-ROCm); the per-pixel HIP kernels and "
@@ -113,6 +117,11 @@ def main(argv=None):
     ap.add_argument("--miopen_benchmark", action=argparse.BooleanOptionalAction, default=False,
                     help="torch.backends.cudnn.benchmark: let MIOpen time its solvers per convolution shape")
     args = ap.parse_args(argv)
+    if args.paper_pwl and args.arch != "curl":
+        raise SystemExit("--paper_pwl is the curve model's (--arch curl)")
+    if args.paper_pwl and args.fused_forward:
+        raise SystemExit("--paper_pwl cannot be combined with --fused_forward: the fused layer-plus-loss forward "
+                         "(curl_layer_loss_fwd_f32) has the reference's affine curves only")
     torch.backends.cudnn.benchmark = bool(args.miopen_benchmark)
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     ddp = args.parallel_mode == "ddp" and world > 1
@@ -132,7 +141,7 @@ def main(argv=None):
         dd = data.filter_data_dict(data.get_data_dict(root), data.get_data_ids(os.path.join(root, "images_inference.txt")))
         loader = DataLoader(data.Dataset(dd, normaliser=1, is_train=False, crop_h=args.crop, crop_w=args.crop),
                             batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers)
-        net = build_net(args.arch, args.width, sync_bn=False, foreground_masks=args.foreground_masks)
+        net = build_net(args.arch, args.width, sync_bn=False, foreground_masks=args.foreground_masks, paper_pwl=args.paper_pwl)
         ckpt = torch.load(args.checkpoint_filepath, map_location="cpu")
         net.load_state_dict(convert_state_dict(ckpt["model_state_dict"]))  # DP/DDP "module." prefixes removed
         net = net.to(device).eval()
@@ -163,7 +172,8 @@ def main(argv=None):
     valid_loader = DataLoader(valid_set, batch_size=args.batch_size, shuffle=False, pin_memory=True,
                               num_workers=args.num_workers, sampler=valid_sampler)
 
-    net = build_net(args.arch, args.width, sync_bn=ddp and args.backend == "nccl", foreground_masks=args.foreground_masks).to(device)
+    net = build_net(args.arch, args.width, sync_bn=ddp and args.backend == "nccl", foreground_masks=args.foreground_masks,
+                    paper_pwl=args.paper_pwl).to(device)
     if args.channels_last:
         net = net.to(memory_format=torch.channels_last)
     autocast = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.amp == "bf16" else contextlib.nullcontext

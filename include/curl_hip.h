@@ -211,6 +211,22 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind,
                        int B, int H, int W, int Kl, int Kr, int Kh,
                        unsigned flags, curl_stream_t stream);
 
+/* replaces: torch autograd through CURLLayer.forward with the paper's piecewise-linear curves, i.e. the backward of
+ *           curl_layer_fwd_f32(..., CURL_F_PWL).  Same arguments, outputs and two passes as curl_layer_bwd_f32; the
+ *           per-pixel pass writes n_knots block partials per workgroup (every curve owes one sum per knot).
+ * Knot counts: even splits only (CURL_K_UNEVEN is CURL_E_KNOTS, as in the PWL forward), 2..CURL_MAX_KNOTS per curve.
+ * scratch: curl_layer_pwl_bwd_scratch_bytes(B,H,W,Kl,Kr,Kh) bytes.
+ * flags: CURL_F_WS_READY (the workspace curl_layer_fwd_f32(..., CURL_F_PWL) filled for the same knots; rows are
+ * stamp-checked), CURL_F_MASK_FIRST; every other bit is CURL_E_FLAGS.  Results are reproducible: no float atomics. */
+size_t curl_layer_pwl_bwd_scratch_bytes(int B, int H, int W, int Kl, int Kr, int Kh);
+int curl_layer_pwl_bwd_f32(const float* img, const void* mask, int mask_kind,
+                           const float* rawL, const float* rawR, const float* rawH,
+                           const float* grad_out, const float* grad_reg,
+                           float* grad_img, float* grad_rawL, float* grad_rawR, float* grad_rawH,
+                           void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                           int B, int H, int W, int Kl, int Kr, int Kh,
+                           unsigned flags, curl_stream_t stream);
+
 /* Backward of the stand-alone curve ops, converters and fused stages above: what torch autograd runs through the
  * reference's plain-torch curves.py / colors.py functions.  Same two passes as curl_layer_bwd_f32 (one over the pixels,
  * forward recomputed in registers; one per image for the knots), for one knot segment.
