@@ -200,6 +200,8 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/stream.inc"
 #include "kernels/ops.inc"
 #include "kernels/chain.inc"
+#include "kernels/reduce.inc"
+#include "kernels/bwd_tile.inc"
 #include "kernels/layer_bwd.inc"
 #include "kernels/layer_pwl_bwd.inc"
 #include "kernels/stage_bwd.inc"

@@ -35,17 +35,18 @@ static bool planes_vec4(size_t HW, const void* mask, int mask_kind, const void* 
   if (mask_kind == CURL_MASK_U8 && ((uintptr_t)mask % 4)) ok = false;
   return ok;
 }
-#define DISPATCH_VEC_MASK(LAUNCH, aligned, mask_kind)                  \
-  do {                                                                 \
-    if (aligned) {                                                     \
-      if ((mask_kind) == CURL_MASK_U8) LAUNCH(4, CURL_MASK_U8);        \
-      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(4, CURL_MASK_F32); \
-      else LAUNCH(4, CURL_MASK_NONE);                                  \
-    } else {                                                           \
-      if ((mask_kind) == CURL_MASK_U8) LAUNCH(1, CURL_MASK_U8);        \
-      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(1, CURL_MASK_F32); \
-      else LAUNCH(1, CURL_MASK_NONE);                                  \
-    }                                                                  \
+// LAUNCH(VEC, MASK, ...) over (aligned, mask_kind); what follows mask_kind is handed on to LAUNCH
+#define DISPATCH_VEC_MASK(LAUNCH, aligned, mask_kind, ...)                            \
+  do {                                                                                \
+    if (aligned) {                                                                    \
+      if ((mask_kind) == CURL_MASK_U8) LAUNCH(4, CURL_MASK_U8, ##__VA_ARGS__);        \
+      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(4, CURL_MASK_F32, ##__VA_ARGS__); \
+      else LAUNCH(4, CURL_MASK_NONE, ##__VA_ARGS__);                                  \
+    } else {                                                                          \
+      if ((mask_kind) == CURL_MASK_U8) LAUNCH(1, CURL_MASK_U8, ##__VA_ARGS__);        \
+      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(1, CURL_MASK_F32, ##__VA_ARGS__); \
+      else LAUNCH(1, CURL_MASK_NONE, ##__VA_ARGS__);                                  \
+    }                                                                                 \
   } while (0)
 
 constexpr unsigned kXcdDefault = 1;  // library default of the workgroup -> tile mapping: 1 = plain, 2 = XCD-contiguous
@@ -547,6 +548,50 @@ static int bwd_prologue(const float* img, const float* grad_out, const void* mas
   return (flags & CURL_F_WS_READY) ? 0 : launch_prep(prep, B, s);
 }
 
+// What the three per-pixel backward kernels are launched with, once the checks are through: the tile's arguments
+// (bwd_tile.inc), one 256-thread block per tile and image, and whether the float4 kernels apply.
+static int bwd_tile_setup(BwdArgs& a, dim3& grid, bool& aligned, const float* img, const float* grad_out, float* grad_img,
+                          const void* mask, int mask_kind, const float* ws, unsigned stride, int n_knots, void* scratch, int B,
+                          int H, int W, unsigned flags) {
+  const size_t HW = (size_t)H * W;
+  aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
+  a.in = img;
+  a.gout = grad_out;
+  a.gin = grad_img;
+  a.mask = mask_kind ? mask : nullptr;
+  a.coef = ws;
+  a.partial = (float*)scratch;
+  a.coef_stride = stride;
+  a.n = (unsigned)(HW / (aligned ? 4 : 1));
+  a.blocks_per_image = (a.n + 255u) / 256u;
+  const uint64_t nb = (uint64_t)a.blocks_per_image * (uint64_t)B;
+  if (nb > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
+  a.n_blocks = (unsigned)nb;
+  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
+  a.stamp = ws_stamp((unsigned)n_knots, stride);
+  grid = dim3(a.blocks_per_image, (unsigned)B);
+  return 0;
+}
+// ... and the launch: KERNEL(V, M, GIN) names the instantiation; `a`, `grid` and the stream `s` are the caller's
+#define LAUNCH_BWD_TILE(V, M, KERNEL, lds)                                                 \
+  do {                                                                                     \
+    if (a.gin) hipLaunchKernelGGL((KERNEL(V, M, true)), grid, dim3(256), lds, s, a);       \
+    else hipLaunchKernelGGL((KERNEL(V, M, false)), grid, dim3(256), lds, s, a);            \
+  } while (0)
+// The second pass of the two layer forms (knots_bwd_kernel, layer_pwl_knots_bwd_kernel) takes the same arguments.
+static KnotsBwdArgs knots_bwd_args(const float* ws, const void* scratch, const float* grad_reg, float* grad_rawL, float* grad_rawR,
+                                   float* grad_rawH, int Kl, int Kr, int Kh, unsigned stride, unsigned blocks_per_image) {
+  KnotsBwdArgs kb;
+  kb.ws = ws;
+  kb.partial = (const float*)scratch;
+  kb.greg = grad_reg;
+  kb.graw[0] = grad_rawL, kb.graw[1] = grad_rawR, kb.graw[2] = grad_rawH;
+  kb.K[0] = Kl, kb.K[1] = Kr, kb.K[2] = Kh;
+  kb.ws_stride = stride;
+  kb.blocks_per_image = blocks_per_image;
+  return kb;
+}
+
 // The backward of one knot segment of 3 (adjust_rgb / adjust_lab, the Lab stage) or 4 curves (adjust_hsv, the HSV stage):
 // arguments checked before any HIP call, the knot prep unless CURL_F_WS_READY, stage_bwd_kernel, stage_knots_bwd_kernel.
 template <int OP>
@@ -567,34 +612,19 @@ static int stage_bwd_common(const float* img, const void* mask, int mask_kind, c
   if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
                             n_knots, make_prep(raw, NC, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, nullptr), s))
     return rc;
-  const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
-  StageBwdArgs a;
-  a.in = img;
-  a.gout = grad_out;
-  a.gin = grad_img;
-  a.mask = mask_kind ? mask : nullptr;
-  a.coef = ws;
-  a.partial = (float*)scratch;
-  a.coef_stride = stride;
-  a.n = (unsigned)(HW / (aligned ? 4 : 1));
-  a.blocks_per_image = (a.n + 255u) / 256u;
-  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
-  a.stamp = ws_stamp((unsigned)n_knots, stride);
-  if ((uint64_t)a.blocks_per_image * (uint64_t)B > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
-  const dim3 grid(a.blocks_per_image, (unsigned)B), block(256);
-#define LAUNCH_STAGE_BWD(V, M)                                                                     \
-  do {                                                                                             \
-    if (grad_img) hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, true>), grid, block, 0, s, a);    \
-    else hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, false>), grid, block, 0, s, a);            \
-  } while (0)
+  BwdArgs a;
+  dim3 grid;
+  bool aligned;
+  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
+    return rc;
+#define STAGE_BWD_KERNEL(V, M, G) stage_bwd_kernel<OP, V, M, G>
   if constexpr (OP == STAGE_LAB || OP == STAGE_HSV) {
-    DISPATCH_VEC_MASK(LAUNCH_STAGE_BWD, aligned, mask_kind);
-  } else {
-    if (aligned) LAUNCH_STAGE_BWD(4, CURL_MASK_NONE);
-    else LAUNCH_STAGE_BWD(1, CURL_MASK_NONE);
+    DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, STAGE_BWD_KERNEL, 0);
+  } else {  // no mask argument: only the CURL_MASK_NONE kernels exist
+    if (aligned) LAUNCH_BWD_TILE(4, CURL_MASK_NONE, STAGE_BWD_KERNEL, 0);
+    else LAUNCH_BWD_TILE(1, CURL_MASK_NONE, STAGE_BWD_KERNEL, 0);
   }
-#undef LAUNCH_STAGE_BWD
+#undef STAGE_BWD_KERNEL
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, name);
   StageKnotsArgs kb;
@@ -859,45 +889,17 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
   if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
                             n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s))
     return rc;
-  const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
   BwdArgs a;
-  a.in = img;
-  a.gout = grad_out;
-  a.gin = grad_img;
-  a.mask = mask_kind ? mask : nullptr;
-  a.coef = ws;
-  a.partial = (float*)scratch;
-  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
-  a.coef_stride = stride;
-  a.stamp = ws_stamp((unsigned)n_knots, stride);
-  a.n = (unsigned)(HW / (aligned ? 4 : 1));
-  a.blocks_per_image = (a.n + 255u) / 256u;
-  uint64_t nb = (uint64_t)a.blocks_per_image * (uint64_t)B;
-  if (nb > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
-  a.n_blocks = (unsigned)nb;
-  dim3 grid(a.blocks_per_image, (unsigned)B), block(256);
-  KnotsBwdArgs kb;
-  kb.ws = ws;
-  kb.partial = (const float*)scratch;
-  kb.greg = grad_reg;
-  kb.graw[0] = grad_rawL;
-  kb.graw[1] = grad_rawR;
-  kb.graw[2] = grad_rawH;
-  kb.K[0] = Kl;
-  kb.K[1] = Kr;
-  kb.K[2] = Kh;
-  kb.ws_stride = stride;
-  kb.blocks_per_image = a.blocks_per_image;
-#define LAUNCH_BWD(V, M)                                                                        \
-  do {                                                                                          \
-    if (grad_img) hipLaunchKernelGGL((layer_bwd_kernel<V, M, true>), grid, block, 0, s, a);     \
-    else hipLaunchKernelGGL((layer_bwd_kernel<V, M, false>), grid, block, 0, s, a);             \
-  } while (0)
-  DISPATCH_VEC_MASK(LAUNCH_BWD, aligned, mask_kind);
-#undef LAUNCH_BWD
+  dim3 grid;
+  bool aligned;
+  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
+    return rc;
+#define LAYER_BWD_KERNEL(V, M, G) layer_bwd_kernel<V, M, G>
+  DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, LAYER_BWD_KERNEL, 0);
+#undef LAYER_BWD_KERNEL
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "layer_bwd_kernel");
+  const KnotsBwdArgs kb = knots_bwd_args(ws, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, stride, a.blocks_per_image);
   hipLaunchKernelGGL(knots_bwd_kernel, dim3(B), dim3(KNOTS_BWD_THREADS), 0, s, kb);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "knots_bwd_kernel");
@@ -932,41 +934,18 @@ int curl_layer_pwl_bwd_f32(const float* img, const void* mask, int mask_kind, co
                             n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s, need,
                             "scratch missing, misaligned or smaller than curl_layer_pwl_bwd_scratch_bytes"))
     return rc;
-  const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
   PwlBwdArgs a;
-  a.in = img;
-  a.gout = grad_out;
-  a.gin = grad_img;
-  a.mask = mask_kind ? mask : nullptr;
-  a.ws = ws;
-  a.partial = (float*)scratch;
-  a.ws_stride = stride;
-  a.n = (unsigned)(HW / (aligned ? 4 : 1));
-  a.blocks_per_image = (a.n + 255u) / 256u;
+  dim3 grid;
+  bool aligned;
+  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
+    return rc;
   a.kl = Kl, a.kr = Kr, a.kh = Kh;
-  a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
-  a.stamp = ws_stamp((unsigned)n_knots, stride);
-  if ((uint64_t)a.blocks_per_image * (uint64_t)B > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
-  const dim3 grid(a.blocks_per_image, (unsigned)B), block(256);
-  const size_t lds = pwl_bwd_lds_bytes(Kl, Kr, Kh);
-#define LAUNCH_PWL_BWD(V, M)                                                                          \
-  do {                                                                                                \
-    if (grad_img) hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, true>), grid, block, lds, s, a);     \
-    else hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, false>), grid, block, lds, s, a);             \
-  } while (0)
-  DISPATCH_VEC_MASK(LAUNCH_PWL_BWD, aligned, mask_kind);
-#undef LAUNCH_PWL_BWD
+#define PWL_BWD_KERNEL(V, M, G) layer_pwl_bwd_kernel<V, M, G>
+  DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, PWL_BWD_KERNEL, pwl_bwd_lds_bytes(Kl, Kr, Kh));
+#undef PWL_BWD_KERNEL
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "layer_pwl_bwd_kernel");
-  PwlKnotsBwdArgs kb;
-  kb.ws = ws;
-  kb.partial = (const float*)scratch;
-  kb.greg = grad_reg;
-  kb.graw[0] = grad_rawL, kb.graw[1] = grad_rawR, kb.graw[2] = grad_rawH;
-  kb.K[0] = Kl, kb.K[1] = Kr, kb.K[2] = Kh;
-  kb.ws_stride = stride;
-  kb.blocks_per_image = a.blocks_per_image;
+  const KnotsBwdArgs kb = knots_bwd_args(ws, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, stride, a.blocks_per_image);
   hipLaunchKernelGGL(layer_pwl_knots_bwd_kernel, dim3(MAX_CURVES, (unsigned)B), dim3(PWL_KNOTS_THREADS), 0, s, kb);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "layer_pwl_knots_bwd_kernel");

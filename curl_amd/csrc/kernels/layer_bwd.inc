@@ -3,108 +3,8 @@
 // backward of the fused layer
 // ------------------------------------------------------------------------------------------------
 #define BWD_NACC 20  // P[10], Q[10]
-struct BwdArgs {
-  const float* in;
-  const float* gout;
-  float* gin;         // nullable
-  const void* mask;
-  const float* coef;  // workspace (prep output)
-  float* partial;     // [n_blocks][BWD_NACC] block partial sums of P,Q
-  unsigned coef_stride, n, blocks_per_image, n_blocks;
-  int mask_first;  // CURL_F_MASK_FIRST: test the mask before the six plane loads go out
-  unsigned stamp;  // ws_stamp of the knot count / row stride this call's workspace rows must have been prepared for
-};
 
-// wave-wide sum in 6 DPP adds (VALU rate; __shfl_xor compiles to ds_bpermute + a full wait each): the row's 16
-// lanes by quad_perm / half-mirror / mirror, then row_bcast15 and row_bcast31.  The total is in lane 63.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float x) {
-  return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xF, false));
-}
-// stage-major over a lane's M accumulators: consecutive DPP adds are independent (no wait states between them)
-template <int CTRL, int ROW_MASK, int R, int M>
-__device__ __forceinline__ void dpp_add_all(float (&x)[R][M]) {
-#pragma unroll
-  for (int o = 0; o < R; ++o)
-#pragma unroll
-    for (int j = 0; j < M; ++j) x[o][j] = dpp_add<CTRL, ROW_MASK>(x[o][j]);
-  CURL_FENCE();
-}
-template <int R, int M>
-__device__ __forceinline__ void wave_sum_lane63(float (&x)[R][M]) {
-  dpp_add_all<0xB1, 0xF>(x);   // quad_perm [1,0,3,2]
-  dpp_add_all<0x4E, 0xF>(x);   // quad_perm [2,3,0,1]
-  dpp_add_all<0x141, 0xF>(x);  // row_half_mirror
-  dpp_add_all<0x140, 0xF>(x);  // row_mirror: every lane of a row holds the row's sum
-  dpp_add_all<0x142, 0xA>(x);  // row_bcast15 into rows 1 and 3
-  dpp_add_all<0x143, 0xC>(x);  // row_bcast31 into rows 2 and 3
-}
-// Wave-wide sums of MANY per-lane values (the polynomial backward reduces 3 x 126 per block): the first two stages trade
-// lanes between two registers instead of adding a shuffled copy to each -- v_permlane32_swap puts the two 32-lane halves
-// of value A into one register's lower half and those of value B into its upper half (one add then serves both),
-// v_permlane16_swap does the same with 16-lane rows -- so four values share one register for the four in-row DPP steps:
-// 2 swaps + 3 adds + 4 DPP adds per FOUR values instead of 6 DPP adds per value.  dst[i] = sum over the wave of x[i].
-__device__ __forceinline__ void lane_swap32(float& a, float& b) {  // a.hi32 <-> b.lo32
-  typedef unsigned u2 __attribute__((ext_vector_type(2)));
-  u2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x), b = __uint_as_float(r.y);
-}
-__device__ __forceinline__ void lane_swap16(float& a, float& b) {  // rows of 16 lanes: a.row1 <-> b.row0, a.row3 <-> b.row2
-  typedef unsigned u2 __attribute__((ext_vector_type(2)));
-  u2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r.x), b = __uint_as_float(r.y);
-}
-template <int N>
-__device__ __forceinline__ void wave_sum_many(const float (&x)[N], float* dst, int lane_id) {
-  constexpr int NQ = (N + 3) / 4;
-  float z[1][NQ];
-#pragma unroll
-  for (int j = 0; j < NQ; ++j) {
-    float v0 = x[4 * j], v1 = 4 * j + 1 < N ? x[4 * j + 1] : 0.0f, v2 = 4 * j + 2 < N ? x[4 * j + 2] : 0.0f,
-          v3 = 4 * j + 3 < N ? x[4 * j + 3] : 0.0f;
-    lane_swap32(v0, v1);
-    lane_swap32(v2, v3);
-    float y0 = v0 + v1, y1 = v2 + v3;  // lanes 0-31 / 32-63: half sums of values 4j / 4j+1, and of 4j+2 / 4j+3
-    lane_swap16(y0, y1);
-    z[0][j] = y0 + y1;  // rows 0..3: values 4j, 4j+2, 4j+1, 4j+3, each summed over four lanes
-  }
-  CURL_FENCE();
-  dpp_add_all<0xB1, 0xF>(z);   // quad_perm [1,0,3,2]
-  dpp_add_all<0x4E, 0xF>(z);   // quad_perm [2,3,0,1]
-  dpp_add_all<0x141, 0xF>(z);  // row_half_mirror
-  dpp_add_all<0x140, 0xF>(z);  // row_mirror: every lane of a row holds the row's sum
-  if ((lane_id & 15) == 0) {
-    const int row = lane_id >> 4, off = ((row & 1) << 1) | (row >> 1);
-#pragma unroll
-    for (int j = 0; j < NQ; ++j)
-      if (4 * j + off < N) dst[4 * j + off] = z[0][j];
-  }
-}
-// A thread's walk over a strided series of float32 block partials, summed in float64: p[j], p[j + step], ... below n.
-// Eight loads in flight and eight partial sums per thread (element u of every group of eight goes to sum u; the tail one element
-// per sum, in order), added in a fixed tree: the order depends on (j, step, n) only -- bit-reproducible.  Written as
-// `for (...) v += p[j]` the walk is one dependent load + add per step, a memory latency each: knots_bwd_kernel's was 16 us of a
-// 120 us backward (round 3); the loss terms' and the polynomial coefficients' second passes got the same form in round 5
-// (5.6 / 7.5 us each for a few thousand floats per image; the PSNR's two short series are faster as a plain loop).
-__device__ __forceinline__ double walk_sum8(const float* p, size_t j, size_t step, size_t n) {
-  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (; j + 7 * step < n; j += 8 * step) {
-    float f[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) f[u] = p[j + u * step];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] += (double)f[u];
-  }
-  {
-    float f[7];
-#pragma unroll
-    for (int u = 0; u < 7; ++u) f[u] = (j + u * step < n) ? p[j + u * step] : 0.0f;  // the tail's loads go out together too
-#pragma unroll
-    for (int u = 0; u < 7; ++u) v[u] += (double)f[u];
-  }
-  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-}
-// One tile per block, like the forward.  Per-pixel reverse mode (curl_math_bwd.h) recomputes the forward
+// One tile per block (bwd_tile.inc).  Per-pixel reverse mode (curl_math_bwd.h) recomputes the forward
 // chain in registers; the 20 per-image curve sums are reduced wave -> LDS -> one row of `partial` per block
 // (no float atomics: the second pass sums the rows in a fixed order in float64, so results are reproducible).
 constexpr int kBwdWaves = 1;  // waves per SIMD the register allocation is held to (1: unconstrained -- 154 VGPRs, three waves)
@@ -113,63 +13,26 @@ constexpr int kBwdWaves = 1;  // waves per SIMD the register allocation is held 
 template <int VEC, int MK, bool GIN = true>
 __global__ __launch_bounds__(256, kBwdWaves) void layer_bwd_kernel(BwdArgs a) {
   typedef typename Pack<VEC>::T T;
-  typedef typename Pack<VEC>::M M;
   __shared__ float sPart[4][BWD_NACC];
   const unsigned img = blockIdx.y;
   const unsigned chunk = blockIdx.x;
   const unsigned bid = img * a.blocks_per_image + chunk;
   const LayerCoef k = OpLayer::load(a.coef + (size_t)img * a.coef_stride, StreamArgs{});
-  const size_t plane = (size_t)a.n;
-  const T* p0 = reinterpret_cast<const T*>(a.in) + (size_t)img * 3 * plane;
-  const T* g0 = reinterpret_cast<const T*>(a.gout) + (size_t)img * 3 * plane;
-  const unsigned i = chunk * 256u + threadIdx.x;
-  const unsigned ic = min(i, a.n - 1u);
-  const bool valid = i < a.n;
-  constexpr bool kNT = VEC == 4;  // streaming data, touched once (stream.inc)
-  T mf;
-  M mb;
-  // A wavefront whose pixels are all masked out (bool / uint8 masks: data.py:190's segmentation masks) has nothing to
-  // compute: every gradient it would produce is an exact zero (curl_math_bwd.h, the binary specialisation).  It skips the
-  // arithmetic -- and, with CURL_F_MASK_FIRST, asks for its mask bytes first and never reads its six planes.
-  bool dead = false;
-  T x0, x1, x2, w0, w1, w2;  // (left undefined for a dead wave: nothing reads them)
-  if constexpr (MK == CURL_MASK_U8) {
-    if (a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (!dead) {
-    x0 = ld<kNT>(at(p0, ic)), x1 = ld<kNT>(at(p0 + plane, ic)), x2 = ld<kNT>(at(p0 + 2 * plane, ic));
-    w0 = ld<kNT>(at(g0, ic)), w1 = ld<kNT>(at(g0 + plane, ic)), w2 = ld<kNT>(at(g0 + 2 * plane, ic));
-  } else {
-    // "defined" without an instruction (left plainly undefined, the compiler zero-fills all 24 registers in front of the branch)
-    asm volatile("" : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(w0), "=v"(w1), "=v"(w2));
-  }
-  if constexpr (MK == CURL_MASK_U8) {
-    if (!a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (MK == CURL_MASK_F32) mf = ld<kNT>(at(reinterpret_cast<const T*>(a.mask) + (size_t)img * plane, ic));
+  BwdTile<VEC, MK, GIN> tile;
+  tile.load(a.in, a.gout, a.mask, img, chunk, a.n, a.mask_first);
   float acc[BWD_NACC];
 #pragma unroll
   for (int c = 0; c < BWD_NACC; ++c) acc[c] = 0.0f;
   T y0, y1, y2;
   float dep = 0.0f;
-  if (GIN && dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
-  if (!dead)
+  if (GIN && tile.dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
+  if (!tile.dead)
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
-    float m = 1.0f;
-    if (MK == CURL_MASK_U8) m = mlane(mb, e);
-    if (MK == CURL_MASK_F32) m = lane(mf, e);
-    if (!valid) m = 0.0f;  // lanes past the end contribute nothing (m multiplies every path to P, Q)
-    Px pin{lane(x0, e), lane(x1, e), lane(x2, e)}, gin{lane(w0, e), lane(w1, e), lane(w2, e)};
-    // one pixel after the other: left free, the compiler interleaves the reverse-mode chains of a lane's four pixels and
-    // their tapes multiply the VGPR count (round 2: 225, two waves per SIMD).  An empty asm makes this pixel's inputs
-    // depend on the previous pixel's result (a scheduling fence alone does not shorten the live ranges).
+    float m = tile.m(e);
+    Px pin = tile.pin(e), gin = tile.gin(e);
+    if (!tile.valid()) m = 0.0f;  // lanes past the end contribute nothing (m multiplies every path to P, Q)
+    // one pixel after the other (bwd_tile.inc, at BwdTile::m)
     asm volatile("" : "+v"(pin.c0), "+v"(pin.c1), "+v"(pin.c2), "+v"(gin.c0), "+v"(gin.c1), "+v"(gin.c2) : "v"(dep));
     // bool / uint8 / no mask: m is exactly 0 or 1 (the binary specialisation); the curve sums go straight into `acc`
     Px gi = curl_layer_bwd<MK != CURL_MASK_F32, GIN>(pin, m, k, gin, acc, acc + 10);
@@ -180,39 +43,15 @@ __global__ __launch_bounds__(256, kBwdWaves) void layer_bwd_kernel(BwdArgs a) {
       set_lane(y2, e, gi.c2);
     }
   }
-  if (GIN && a.gin && valid) {
-    // The coefficients came from the image's workspace row.  With CURL_F_WS_READY the caller vouches for it; a row nobody
-    // prepared for this call's knot counts (a zeroed buffer, another K) must not turn into a plausible-looking gradient image:
-    // the workgroup stores NaN instead of what it computed (knots_bwd_kernel does the same for the knot gradients).  One scalar
-    // load per wave, here at the end: held from the start it would be one more live SGPR in a kernel that has none to spare.
-    // A BRANCH around two store sequences (the asm keeps it one): as `y = bad ? NaN : y` it was twelve selects per lane on the
-    // product path, +1.3 % per 8 frames (profiles/r05/ab_r05_vs_r04_library.log).
-    T* q0 = reinterpret_cast<T*>(a.gin) + (size_t)img * 3 * plane;
-    if (__builtin_expect(reinterpret_cast<const unsigned*>(a.coef + (size_t)img * a.coef_stride)[WS_STAMP] != a.stamp, 0)) {
-      T nan_t = T(__builtin_nanf(""));
-      asm volatile("" : "+v"(nan_t));
-      st<kNT>(at(q0, i), nan_t);
-      st<kNT>(at(q0 + plane, i), nan_t);
-      st<kNT>(at(q0 + 2 * plane, i), nan_t);
-    } else {
-      st<kNT>(at(q0, i), y0);
-      st<kNT>(at(q0 + plane, i), y1);
-      st<kNT>(at(q0 + 2 * plane, i), y2);
-    }
+  if constexpr (GIN) {
+    if (a.gin) tile.store(a.gin, a.coef + (size_t)img * a.coef_stride, a.stamp, y0, y1, y2);
   }
-  // wave sums by lane swaps + in-row DPP (wave_sum_many), then the 4 waves through LDS
-  const int wave = threadIdx.x >> 6, lane_id = threadIdx.x & 63;
-  wave_sum_many(acc, sPart[wave], lane_id);
-  __syncthreads();
-  if (threadIdx.x < BWD_NACC) {
-    int c = threadIdx.x;
-    a.partial[(size_t)bid * BWD_NACC + c] = (sPart[0][c] + sPart[1][c]) + (sPart[2][c] + sPart[3][c]);
-  }
+  block_row_sum(acc, sPart, a.partial, bid);
 }
 
 struct KnotsBwdArgs {
   const float* ws;       // prep output (exp'd knots at WS_KNOTS)
-  const float* partial;  // [B][blocks_per_image][BWD_NACC]
+  const float* partial;  // [B][blocks_per_image][row]: BWD_NACC floats per row, n_knots for the PWL layer
   const float* greg;     // nullable [B]
   float* graw[3];        // gradients shaped like rawL, rawR, rawH
   int K[3];

@@ -6,17 +6,8 @@
 // row of block partials; a per-image pass sums the rows in a fixed order in float64 and applies the chain rule.  What differs is
 // the width of a row: a PWL curve of K knots owes K sums (curl_math_bwd.h curl_layer_pwl_bwd: sum G and sum G clamp01(s - j),
 // j = 0 .. K-2) instead of the affine form's two, so a row is n_knots floats -- curve after curve, in the knots' own order.
-struct PwlBwdArgs {
-  const float* in;
-  const float* gout;
-  float* gin;         // nullable
-  const void* mask;
-  const float* ws;    // workspace (prep output: exp'd knots at WS_KNOTS, the row stamp)
-  float* partial;     // [n_blocks][n_knots] block partial sums
-  unsigned ws_stride, n, blocks_per_image;
-  int kl, kr, kh;     // knots per curve (even splits only)
-  int mask_first;     // CURL_F_MASK_FIRST
-  unsigned stamp;     // ws_stamp this call's workspace rows must carry
+struct PwlBwdArgs : BwdArgs {  // the tile's arguments (bwd_tile.inc; partial rows are n_knots floats), and
+  int kl, kr, kh;              // knots per curve (even splits only)
 };
 
 // The 16-wide chunks of a curve's sums: index t of a curve is sum G (t = 0) or sum G clamp01(s - (t - 1)); a curve's LDS slot
@@ -53,7 +44,6 @@ struct PwlTape {
 template <int VEC, int MK, bool GIN = true>
 __global__ __launch_bounds__(256, 1) void layer_pwl_bwd_kernel(PwlBwdArgs a) {
   typedef typename Pack<VEC>::T T;
-  typedef typename Pack<VEC>::M M;
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];
   const int kl = a.kl, kr = a.kr, kh = a.kh;
   const int n_knots = 3 * kl + 3 * kr + 4 * kh;
@@ -64,39 +54,9 @@ __global__ __launch_bounds__(256, 1) void layer_pwl_bwd_kernel(PwlBwdArgs a) {
   const unsigned img = blockIdx.y;
   const unsigned chunk = blockIdx.x;
   const unsigned bid = img * a.blocks_per_image + chunk;
-  const float* row = a.ws + (size_t)img * a.ws_stride;
-  const size_t plane = (size_t)a.n;
-  const T* p0 = reinterpret_cast<const T*>(a.in) + (size_t)img * 3 * plane;
-  const T* g0 = reinterpret_cast<const T*>(a.gout) + (size_t)img * 3 * plane;
-  const unsigned i = chunk * 256u + threadIdx.x;
-  const unsigned ic = min(i, a.n - 1u);
-  const bool valid = i < a.n;
-  constexpr bool kNT = VEC == 4;
-  T mf;
-  M mb;
-  // a wavefront whose pixels are all masked out owes exact zeros (layer_bwd_kernel): with CURL_F_MASK_FIRST it asks for its mask
-  // bytes first and never reads its six planes
-  bool dead = false;
-  T x0, x1, x2, w0, w1, w2;
-  if constexpr (MK == CURL_MASK_U8) {
-    if (a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (!dead) {
-    x0 = ld<kNT>(at(p0, ic)), x1 = ld<kNT>(at(p0 + plane, ic)), x2 = ld<kNT>(at(p0 + 2 * plane, ic));
-    w0 = ld<kNT>(at(g0, ic)), w1 = ld<kNT>(at(g0 + plane, ic)), w2 = ld<kNT>(at(g0 + 2 * plane, ic));
-  } else {
-    asm volatile("" : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(w0), "=v"(w1), "=v"(w2));
-  }
-  if constexpr (MK == CURL_MASK_U8) {
-    if (!a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (MK == CURL_MASK_F32) mf = ld<kNT>(at(reinterpret_cast<const T*>(a.mask) + (size_t)img * plane, ic));
+  const float* row = a.coef + (size_t)img * a.coef_stride;
+  BwdTile<VEC, MK, GIN> tile;
+  tile.load(a.in, a.gout, a.mask, img, chunk, a.n, a.mask_first);
   // the image's table, staged while the pixel loads are in flight: knot j, and slope j = C[j+1] - C[j] inside its curve, 0 for a
   // curve's last knot (OpLayerTab::stage_value, the same floats)
   for (int t = threadIdx.x; t < n_knots; t += 256) {
@@ -110,18 +70,16 @@ __global__ __launch_bounds__(256, 1) void layer_pwl_bwd_kernel(PwlBwdArgs a) {
   const int wave = threadIdx.x >> 6, lane_id = threadIdx.x & 63;
   float* my_part = s_part + wave * n_pad;
   T y0, y1, y2;
-  if (GIN && dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
-  if (!dead) {
+  if (GIN && tile.dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
+  if (!tile.dead) {
     PwlTape<VEC> tape;
     float dep = 0.0f;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      float m = 1.0f;
-      if (MK == CURL_MASK_U8) m = mlane(mb, e);
-      if (MK == CURL_MASK_F32) m = lane(mf, e);
-      if (!valid) m = 0.0f;  // lanes past the end contribute nothing (G = 0 on every curve)
-      Px pin{lane(x0, e), lane(x1, e), lane(x2, e)}, gin{lane(w0, e), lane(w1, e), lane(w2, e)};
-      // one pixel after the other (layer_bwd_kernel: interleaved, the tapes of a lane's pixels multiply the VGPR count)
+      float m = tile.m(e);
+      Px pin = tile.pin(e), gin = tile.gin(e);
+      if (!tile.valid()) m = 0.0f;  // lanes past the end contribute nothing (G = 0 on every curve)
+      // one pixel after the other (bwd_tile.inc, at BwdTile::m)
       asm volatile("" : "+v"(pin.c0), "+v"(pin.c1), "+v"(pin.c2), "+v"(gin.c0), "+v"(gin.c1), "+v"(gin.c2) : "v"(dep));
       tape.e = e;
       Px fwd;
@@ -144,20 +102,8 @@ __global__ __launch_bounds__(256, 1) void layer_pwl_bwd_kernel(PwlBwdArgs a) {
   } else {
     for (int t = lane_id; t < n_pad; t += 64) my_part[t] = 0.0f;
   }
-  if (GIN && a.gin && valid) {
-    // a workspace row nobody prepared for this call's knot counts gives NaN, not a plausible gradient image (layer_bwd_kernel)
-    T* q0 = reinterpret_cast<T*>(a.gin) + (size_t)img * 3 * plane;
-    if (__builtin_expect(reinterpret_cast<const unsigned*>(row)[WS_STAMP] != a.stamp, 0)) {
-      T nan_t = T(__builtin_nanf(""));
-      asm volatile("" : "+v"(nan_t));
-      st<kNT>(at(q0, i), nan_t);
-      st<kNT>(at(q0 + plane, i), nan_t);
-      st<kNT>(at(q0 + 2 * plane, i), nan_t);
-    } else {
-      st<kNT>(at(q0, i), y0);
-      st<kNT>(at(q0 + plane, i), y1);
-      st<kNT>(at(q0 + 2 * plane, i), y2);
-    }
+  if constexpr (GIN) {
+    if (a.gin) tile.store(a.gin, row, a.stamp, y0, y1, y2);
   }
   __syncthreads();
   // the block's row: the four waves' sums added in a fixed order, in the knots' layout (curve c at its first knot)
@@ -177,20 +123,11 @@ static inline size_t pwl_bwd_lds_bytes(int kl, int kr, int kh) {
   return (size_t)(2 * n_knots + 4 * n_pad) * sizeof(float);
 }
 
-struct PwlKnotsBwdArgs {
-  const float* ws;       // prep output (exp'd knots at WS_KNOTS)
-  const float* partial;  // [B][blocks_per_image][n_knots]
-  const float* greg;     // nullable [B]
-  float* graw[3];        // gradients shaped like rawL, rawR, rawH
-  int K[3];
-  unsigned ws_stride, blocks_per_image;
-};
-
 // One workgroup per (curve, image): thread t < phases * K walks column t % K of the curve's slice of the rows, every
 // phases-th row from row t / K (walk_sum8: eight loads in flight, float64), then the phase sums of a column are added in phase
 // order -- a fixed order, bit-reproducible -- and each knot gets the chain rule (curl_math_bwd.h knot_bwd_pwl).
 #define PWL_KNOTS_THREADS 1024
-__global__ __launch_bounds__(PWL_KNOTS_THREADS) void layer_pwl_knots_bwd_kernel(PwlKnotsBwdArgs a) {
+__global__ __launch_bounds__(PWL_KNOTS_THREADS) void layer_pwl_knots_bwd_kernel(KnotsBwdArgs a) {
   __shared__ double sAcc[PWL_KNOTS_THREADS];
   __shared__ double sT[CURL_MAX_KNOTS];
   const unsigned c = blockIdx.x, b = blockIdx.y;

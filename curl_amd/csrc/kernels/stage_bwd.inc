@@ -7,7 +7,9 @@
 // kernel recomputes the stage's forward tape in registers (curl_math_bwd.h: adjust3_bwd, adjust_hsv_bwd, lab_stage_bwd,
 // hsv_stage_bwd), writes the image gradient and reduces its curves' sums P, Q to one row of block partials (no float
 // atomics); a per-image kernel sums the rows in a fixed order in float64 and applies the chain rule to the raw knots.
-// These are siblings of layer_bwd_kernel / knots_bwd_kernel, not re-templated forms of them: those two are benchmarked.
+// The tile -- addressing, the mask protocol, the guarded store of grad_img, the block's row of partials -- is the one
+// layer_bwd_kernel uses (bwd_tile.inc).  The pullbacks and the second-pass kernels stay separate: knots_bwd_kernel is tuned
+// for the layer's ten curves (1024 threads, knot_bwd5, its loads asked for early) and is benchmarked.
 #define STAGE_ADJ3 0  // adjust_rgb / adjust_lab: OpAdjust3 in the forward
 #define STAGE_AHSV 1  // adjust_hsv
 #define STAGE_LAB 2   // rgb2lab -> adjust3 -> *mask -> lab2rgb
@@ -18,18 +20,6 @@ struct StageCurves {
 };
 #define STAGE_NACC_MAX 8  // P[4], Q[4]
 
-struct StageBwdArgs {
-  const float* in;
-  const float* gout;
-  float* gin;  // nullable
-  const void* mask;
-  const float* coef;  // workspace (prep output)
-  float* partial;     // [n_blocks][2 * curves] block partial sums of P, Q
-  unsigned coef_stride, n, blocks_per_image;
-  int mask_first;  // CURL_F_MASK_FIRST: test the mask before the six plane loads go out
-  unsigned stamp;  // ws_stamp this call's workspace rows must carry
-};
-
 template <int OP, bool BINARY, bool GIN>
 __device__ __forceinline__ Px stage_pixel_bwd(Px in, float m, const Affine* k, Px g, float* P, float* Q) {
   if constexpr (OP == STAGE_ADJ3) return adjust3_bwd(in, k, g, P, Q);
@@ -38,11 +28,10 @@ __device__ __forceinline__ Px stage_pixel_bwd(Px in, float m, const Affine* k, P
   else return hsv_stage_bwd<BINARY, GIN>(in, m, k, g, P, Q);
 }
 
-// One 256-thread workgroup per tile of 256 VEC-groups of one image (as layer_bwd_kernel).  GIN: d loss / d img is wanted.
+// One tile per block (bwd_tile.inc).  GIN: d loss / d img is wanted.
 template <int OP, int VEC, int MK, bool GIN>
-__global__ __launch_bounds__(256) void stage_bwd_kernel(StageBwdArgs a) {
+__global__ __launch_bounds__(256) void stage_bwd_kernel(BwdArgs a) {
   typedef typename Pack<VEC>::T T;
-  typedef typename Pack<VEC>::M M;
   constexpr int NC = StageCurves<OP>::kN, NACC = 2 * NC;
   __shared__ float sPart[4][NACC];
   const unsigned img = blockIdx.y;
@@ -52,53 +41,22 @@ __global__ __launch_bounds__(256) void stage_bwd_kernel(StageBwdArgs a) {
   Affine k[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) k[c] = load_affine(row, c);
-  const size_t plane = (size_t)a.n;
-  const T* p0 = reinterpret_cast<const T*>(a.in) + (size_t)img * 3 * plane;
-  const T* g0 = reinterpret_cast<const T*>(a.gout) + (size_t)img * 3 * plane;
-  const unsigned i = chunk * 256u + threadIdx.x;
-  const unsigned ic = min(i, a.n - 1u);
-  const bool valid = i < a.n;
-  constexpr bool kNT = VEC == 4;
-  T mf;
-  M mb;
-  // a wavefront whose pixels are all masked out (bool / uint8) has nothing to compute: every gradient it owes is an exact 0
-  bool dead = false;
-  T x0, x1, x2, w0, w1, w2;
-  if constexpr (MK == CURL_MASK_U8) {
-    if (a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (!dead) {
-    x0 = ld<kNT>(at(p0, ic)), x1 = ld<kNT>(at(p0 + plane, ic)), x2 = ld<kNT>(at(p0 + 2 * plane, ic));
-    w0 = ld<kNT>(at(g0, ic)), w1 = ld<kNT>(at(g0 + plane, ic)), w2 = ld<kNT>(at(g0 + 2 * plane, ic));
-  } else {
-    asm volatile("" : "=v"(x0), "=v"(x1), "=v"(x2), "=v"(w0), "=v"(w1), "=v"(w2));
-  }
-  if constexpr (MK == CURL_MASK_U8) {
-    if (!a.mask_first) {
-      mb = ld<kNT>(at(reinterpret_cast<const M*>(a.mask) + (size_t)img * plane, ic));
-      dead = __builtin_amdgcn_ballot_w64(valid && mb != 0) == 0ull;
-    }
-  }
-  if (MK == CURL_MASK_F32) mf = ld<kNT>(at(reinterpret_cast<const T*>(a.mask) + (size_t)img * plane, ic));
+  BwdTile<VEC, MK, GIN> tile;
+  tile.load(a.in, a.gout, a.mask, img, chunk, a.n, a.mask_first);
   float acc[NACC];
 #pragma unroll
   for (int c = 0; c < NACC; ++c) acc[c] = 0.0f;
   T y0, y1, y2;
   float dep = 0.0f;
-  if (GIN && dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
-  if (!dead)
+  if (GIN && tile.dead) y0 = T(0.0f), y1 = T(0.0f), y2 = T(0.0f);
+  if (!tile.dead)
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      float m = 1.0f;
-      if (MK == CURL_MASK_U8) m = mlane(mb, e);
-      if (MK == CURL_MASK_F32) m = lane(mf, e);
-      Px pin{lane(x0, e), lane(x1, e), lane(x2, e)}, gin{lane(w0, e), lane(w1, e), lane(w2, e)};
+      float m = tile.m(e);
+      Px pin = tile.pin(e), gin = tile.gin(e);
       // lanes past the end contribute nothing: their incoming gradient is 0 (the stand-alone curves have no mask to carry it)
-      if (!valid) gin = Px{0.0f, 0.0f, 0.0f}, m = 0.0f;
-      // one pixel after the other (layer_bwd_kernel: interleaved reverse-mode chains multiply the live tapes)
+      if (!tile.valid()) gin = Px{0.0f, 0.0f, 0.0f}, m = 0.0f;
+      // one pixel after the other (bwd_tile.inc, at BwdTile::m)
       asm volatile("" : "+v"(pin.c0), "+v"(pin.c1), "+v"(pin.c2), "+v"(gin.c0), "+v"(gin.c1), "+v"(gin.c2) : "v"(dep));
       Px gi = stage_pixel_bwd<OP, MK != CURL_MASK_F32, GIN>(pin, m, k, gin, acc, acc + NC);
       dep = gi.c0;
@@ -108,28 +66,8 @@ __global__ __launch_bounds__(256) void stage_bwd_kernel(StageBwdArgs a) {
         set_lane(y2, e, gi.c2);
       }
     }
-  if (GIN && valid) {
-    // a workspace row nobody prepared for this call's knot count is answered with NaN, never a plausible gradient
-    T* q0 = reinterpret_cast<T*>(a.gin) + (size_t)img * 3 * plane;
-    if (__builtin_expect(reinterpret_cast<const unsigned*>(row)[WS_STAMP] != a.stamp, 0)) {
-      T nan_t = T(__builtin_nanf(""));
-      asm volatile("" : "+v"(nan_t));
-      st<kNT>(at(q0, i), nan_t);
-      st<kNT>(at(q0 + plane, i), nan_t);
-      st<kNT>(at(q0 + 2 * plane, i), nan_t);
-    } else {
-      st<kNT>(at(q0, i), y0);
-      st<kNT>(at(q0 + plane, i), y1);
-      st<kNT>(at(q0 + 2 * plane, i), y2);
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane_id = threadIdx.x & 63;
-  wave_sum_many(acc, sPart[wave], lane_id);
-  __syncthreads();
-  if (threadIdx.x < NACC) {
-    const int c = threadIdx.x;
-    a.partial[(size_t)bid * NACC + c] = (sPart[0][c] + sPart[1][c]) + (sPart[2][c] + sPart[3][c]);
-  }
+  if constexpr (GIN) tile.store(a.gin, row, a.stamp, y0, y1, y2);
+  block_row_sum(acc, sPart, a.partial, bid);
 }
 
 struct StageKnotsArgs {
