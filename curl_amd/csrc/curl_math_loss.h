@@ -150,20 +150,27 @@ CURL_HD float sign0(float x) {
 }
 
 // w * torch.sign(x) in three instructions where `w * sign0(x)` takes four: the second scaling carries the weight,
-// (x 2^100) (2^100 w) has the sign of x w and -- for any nonzero float32 x and |w| >= 1e-15 -- a magnitude far above |w|, so the
-// median with -|w| and +|w| is exactly w sign(x); x = 0 gives 0.  (The weights are d loss / d sum divided by the pixel count:
-// 1e-7 ... 1; an |x| above 2^27 would overflow the first product -- differences of values in [0, 1] do not.)
+// (x 2^100) bw with bw = 2^100 w SATURATED at +-2^127 has the sign of x w and a magnitude of at least |w|, so the median with
+// -|w| and +|w| is exactly w sign(x); x = 0 gives 0 * bw = 0 because bw is finite (as 2^100 w alone it was inf from
+// |w| = 2^28, and every masked-out pixel and every pred == target pixel -- x = 0 -- came out NaN).  Domain:
+//   x   finite, |x| < 2^27: the first product must not overflow (inf * bw is NaN at w = 0).  Differences of colours do not.
+//   w   any finite float32 for x = 0.  For x != 0 the smallest product is |x| 2^100 min(2^100 |w|, 2^127): exact for EVERY
+//       nonzero x, denormals included (2^-149 2^100 2^127 = 2^78), while |w| <= 2^78, and for every normal x
+//       (|x| >= 2^-126) while |w| <= 2^101 = 2.5e30; beyond that the result keeps the sign of x w with a magnitude <= |w|.
+//       (The weights are d loss / d sum divided by the pixel count, 1e-7 ... 1, times whatever the caller scales the loss by.)
+// The saturation is on the weight alone: wave-invariant, no instruction per pixel.
 struct SignW {
-  float bw, aw;  // 2^100 w, |w|
+  float bw, aw;  // 2^100 w saturated at +-2^127, |w|
 };
-CURL_HD SignW signw_of(float w) { return SignW{0x1p100f * w, fabsf(w)}; }
+CURL_HD SignW signw_of(float w) { return SignW{fminf(fmaxf(0x1p100f * w, -0x1p127f), 0x1p127f), fabsf(w)}; }
 CURL_HD float signw(float x, float w, const SignW& k) {
 #if defined(__HIP_DEVICE_COMPILE__)
   (void)w;
   return __builtin_amdgcn_fmed3f((x * 0x1p100f) * k.bw, -k.aw, k.aw);
 #else
-  (void)k;
-  return w * sign0(x);
+  (void)w;  // the same three operations on the host (the median of a, -|w|, |w| is a clamped to [-|w|, |w|]), so the twin
+            // tests hold this formula -- its domain included -- and not `w * sign0(x)`, which has none
+  return fminf(fmaxf((x * 0x1p100f) * k.bw, -k.aw), k.aw);
 #endif
 }
 

@@ -1357,6 +1357,9 @@ int curl_layer_loss_fwd_f32(const float* img, const void* mask, int mask_kind, c
   return 0;
 }
 
+// `weights` is a DEVICE pointer: the host cannot look at it.  Supported: any finite float32 for the three L1 weights (0, 2, 3) --
+// x = 0 (masked out, pred == target) gives exactly 0 for all of them; w sign(x) is exact for |w| <= 2^101 (|w| <= 2^78 when x
+// is denormal), sign-correct beyond; |x| = |pred m - target m| < 2^27.  curl_math_loss.h signw_of, include/curl_hip.h.
 int curl_loss_terms_bwd_f32(const float* pred, const float* target, const void* mask, int mask_kind,
                             const float* weights, const float* grad_L_pred, float* grad_pred, int B, int H, int W,
                             curl_stream_t stream) {

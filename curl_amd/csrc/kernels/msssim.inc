@@ -79,7 +79,16 @@ __global__ __launch_bounds__(256) void msssim_level_kernel(SsimArgs p) {
       // metric.py:139-163
       float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
       float A1 = 2.0f * m12 + C1, B1 = m11 + m22 + C1;
-      float A2 = 2.0f * (e12 - m12) + C2, B2 = (e11 - m11) + (e22 - m22) + C2;
+      // The (co)variances as the reference forms them (metric.py:143-145): blur minus the ROUNDED product of the means.
+      // Contracted into fma(-m1, m1, e11) -- exact product against a rounded blur -- a variance that is 0 (flat regions; any
+      // region under window 1, where the blur of a^2 IS round(a * a)) came out as the rounding residue of the product, up to
+      // 3e-8 against C2 = 9e-4: the per-level means were 1.2e-5 off on a 2x2 plane, where the oracle's float32 is 7e-8 off.
+      float s11, s22, s12;
+      {
+#pragma clang fp contract(off)
+        s11 = e11 - m11, s22 = e22 - m22, s12 = e12 - m12;
+      }
+      float A2 = 2.0f * s12 + C2, B2 = s11 + s22 + C2;
       float rB1 = 1.0f / B1, rB2 = 1.0f / B2;
       float T = A2 * rB2, S = A1 * rB1 * T;
       if (!BACKWARD) {

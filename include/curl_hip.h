@@ -371,7 +371,11 @@ int curl_loss_terms_f32(const float* pred, const float* target, const void* mask
                         float* L_pred, float* L_target, void* scratch, size_t scratch_bytes,
                         int B, int H, int W, curl_stream_t stream);
 /* Backward of the above w.r.t. pred.  weights: DEVICE pointer to 4 floats = d loss / d (each of the four sums);
- * grad_L_pred [B,1,H,W] (nullable): d loss / d L_pred from the MS-SSIM branch.  grad_pred [B,3,H,W] ASSIGNED. */
+ * grad_L_pred [B,1,H,W] (nullable): d loss / d L_pred from the MS-SSIM branch.  grad_pred [B,3,H,W] ASSIGNED.
+ * Domain (the weights live on the device, so nothing here can check them): pred, target finite with |pred * mask -
+ * target * mask| < 2^27; weights[0], [2], [3] (the three L1 terms) any finite float32 -- a masked-out pixel and a pixel
+ * with pred == target get exactly 0, never NaN; w * sign(difference) is exact while |w| <= 2^101 (2.5e30; for a denormal
+ * difference while |w| <= 2^78) and beyond that keeps its sign with a magnitude <= |w|.  weights[1] is a plain factor. */
 int curl_loss_terms_bwd_f32(const float* pred, const float* target, const void* mask, int mask_kind,
                             const float* weights, const float* grad_L_pred, float* grad_pred,
                             int B, int H, int W, curl_stream_t stream);

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import criterion_check as CC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -339,9 +341,10 @@ def test_curl_loss_terms_golden(dev, golden):
         assert (Lt.cpu().numpy() - g[f"{mk}_Lt"]).__abs__().max() <= 1e-6
         total = float(w[0]) * rgb + float(w[1]) * cosv + float(w[2]) * lab + float(w[3]) * hsv + (Lp * wl).sum() * 1e-3
         total.backward()
-        ref = g[f"{mk}_grad_pred"]
-        d = np.abs(pred.grad.cpu().numpy() - ref)
-        assert np.quantile(d, 0.995) <= 2e-4 * np.abs(ref).max() and d.max() <= 5e-2 * np.abs(ref).max()
+        # pixel by pixel against float64 autograd (criterion_check.py): the golden gradient's max, 4.05e4, is the cosine term at 106
+        # black predictions; relative to it (as here until now) a gradient that is zero at every other pixel passed
+        CC.loss_gradient_reference(torch.from_numpy(g["pred"]), torch.from_numpy(g["target"]), m.cpu(), [float(v) for v in w],
+                                   torch.from_numpy(g["wl"]) * 1e-3, label=f"golden, {mk} mask").check(pred.grad)
 
 
 def test_curl_loss_module_vs_oracle(dev):
@@ -350,6 +353,7 @@ def test_curl_loss_module_vs_oracle(dev):
     g = torch.Generator().manual_seed(8)
     pred, tgt = torch.rand(3, 3, 40, 56, generator=g), torch.rand(3, 3, 40, 56, generator=g)
     mask = torch.rand(3, 1, 40, 56, generator=g) > 0.3
+    pred, _ = CC.decidable_inputs(pred, tgt, mask)  # (2 to 7 pixels whose sign float32 cannot decide: criterion_check.py)
     want = O.curl_loss(pred, tgt, mask, torch.tensor(0.0))
     got = model.CURLLoss(msssim_layer=None)(pred.to(dev), tgt.to(dev), mask.to(dev))
     assert abs(float(got) - float(want)) <= 2e-6
@@ -362,8 +366,8 @@ def test_curl_loss_module_vs_oracle(dev):
     ref = (r[0] + r[1] + r[2] + r[3] + 10 * (1.0 - fake_ssim(r[4], r[5])).mean()) / 5
     ref.backward()
     assert abs(float(loss) - float(ref)) <= 2e-6
-    d = (p.grad.cpu() - pc.grad).abs()
-    assert float(torch.quantile(d.flatten(), 0.995)) <= 2e-4 * float(pc.grad.abs().max())
+    extra = lambda Lp, Lt: 2.0 * (1.0 - fake_ssim(Lp, Lt)).mean()  # noqa: E731
+    CC.loss_gradient_reference(pred, tgt, mask, (0.2, 0.2, 0.2, 0.2), extra=extra, label="module, stand-in MS-SSIM").check(p.grad)
 
 
 def test_curl_loss_float_mask_strictly_inside_the_unit_interval(dev):
@@ -375,6 +379,7 @@ def test_curl_loss_float_mask_strictly_inside_the_unit_interval(dev):
     pred, tgt = torch.rand(2, 3, 40, 56, generator=g), torch.rand(2, 3, 40, 56, generator=g)
     soft = torch.rand(2, 1, 40, 56, generator=g) * 0.8 + 0.1
     soft[:, :, :5] = 0.0  # ... and some exact zeros
+    pred, _ = CC.decidable_inputs(pred, tgt, soft)  # (2 to 7 pixels whose sign float32 cannot decide: criterion_check.py)
     p = pred.to(dev).requires_grad_(True)
     got = model.CURLLoss(msssim_layer=None)(p, tgt.to(dev), soft.to(dev))
     got.backward()
@@ -382,8 +387,7 @@ def test_curl_loss_float_mask_strictly_inside_the_unit_interval(dev):
     want = O.curl_loss(pc, tgt.double(), soft.double(), torch.tensor(0.0, dtype=torch.float64))
     want.backward()
     assert abs(float(got) - float(want)) <= 2e-6, (float(got), float(want))
-    d = (p.grad.cpu().double() - pc.grad).abs()
-    assert float(torch.quantile(d.flatten(), 0.995)) <= 2e-4 * float(pc.grad.abs().max())
+    CC.loss_gradient_reference(pred, tgt, soft, (0.2, 0.2, 0.2, 0.2), label="fractional mask").check(p.grad)
 
 
 @pytest.mark.parametrize("kind", ["bool", "binary_float", "fractional_float"])
@@ -398,6 +402,7 @@ def test_curl_loss_one_image_mask_broadcast_over_the_batch(dev, kind):
     pred, tgt = torch.rand(B, 3, 24, 40, generator=g), torch.rand(B, 3, 24, 40, generator=g)
     m = torch.rand(1, 1, 24, 40, generator=g)
     mask = {"bool": m > 0.3, "binary_float": (m > 0.3).float(), "fractional_float": torch.where(m > 0.3, m, torch.zeros(()))}[kind]
+    pred, _ = CC.decidable_inputs(pred, tgt, mask)
     p = pred.to(dev).requires_grad_(True)
     got = model.CURLLoss(msssim_layer=None)(p, tgt.to(dev), mask.to(dev))
     got.backward()
@@ -406,8 +411,7 @@ def test_curl_loss_one_image_mask_broadcast_over_the_batch(dev, kind):
     want = O.curl_loss(pc, tgt.double(), md, torch.tensor(0.0, dtype=torch.float64))
     want.backward()
     assert abs(float(got) - float(want)) <= 3e-6 * max(1.0, abs(float(want))), (float(got), float(want))
-    d = (p.grad.cpu().double() - pc.grad).abs()
-    assert float(torch.quantile(d.flatten(), 0.995)) <= 2e-4 * float(pc.grad.abs().max())
+    CC.loss_gradient_reference(pred, tgt, mask, (0.2, 0.2, 0.2, 0.2), label=f"one-image mask, {kind}").check(p.grad)
     # and the same mask given per image: the L1 terms are then B times smaller, the cosine term the same
     full = model.CURLLoss(msssim_layer=None)(pred.to(dev), tgt.to(dev), mask.expand(B, 1, 24, 40).contiguous().to(dev))
     want_full = O.curl_loss(pred.double(), tgt.double(), md.expand(B, 1, 24, 40), torch.tensor(0.0, dtype=torch.float64))
@@ -423,6 +427,7 @@ def test_curl_loss_with_msssim_vs_oracle(dev):
     tgt = torch.rand(2, 3, 96, 128, generator=g)
     pred = (tgt + 0.08 * torch.randn(2, 3, 96, 128, generator=g)).clamp(0, 1)
     mask = torch.rand(2, 1, 96, 128, generator=g) > 0.2
+    pred, _ = CC.decidable_inputs(pred, tgt, mask)  # (2 to 7 pixels whose sign float32 cannot decide: criterion_check.py)
     crit = model.CURLLoss(ssim_window_size=5).to(dev)
     p = pred.to(dev).requires_grad_(True)
     loss = crit(p, tgt.to(dev), mask.to(dev))
@@ -432,8 +437,8 @@ def test_curl_loss_with_msssim_vs_oracle(dev):
     ref = O.curl_loss(pc, tgt, mask, (1.0 - O.msssim(r[4], r[5], 11, 1)).mean())
     ref.backward()
     assert abs(float(loss) - float(ref)) <= 5e-6
-    d = (p.grad.cpu() - pc.grad).abs()
-    assert float(torch.quantile(d.flatten(), 0.995)) <= 5e-4 * float(pc.grad.abs().max())
+    # (the gradient's max, 603, is ONE black prediction against 4.5e-4 elsewhere: 5e-4 of it was an absolute 0.3)
+    CC.criterion_reference(pred, tgt, mask, "criterion with MS-SSIM").check(p.grad)
 
 
 @pytest.mark.parametrize("nc,residual_only,shape", [(126, False, (2, 12, 20)), (126, True, (1, 70, 131)),

@@ -52,6 +52,12 @@ def test_twin_backward(twin, golden):
     d = np.abs(got - ref)
     scale = np.abs(ref).max()
     assert np.quantile(d, 0.995) <= 2e-4 * scale and d.max() <= 5e-2 * scale
+    # `scale` is the cosine gradient of 106 black predictions, 4.05e4, against 5.5e-3 at every other pixel: the line above
+    # alone would pass a gradient that is zero everywhere else.  Pixel by pixel against float64 (criterion_check.py):
+    import criterion_check as CC
+    pred, tgt, mask = torch.from_numpy(g["pred"]), torch.from_numpy(g["target"]), torch.from_numpy(g["mask"])
+    check = CC.loss_gradient_reference(pred, tgt, mask, [float(v) for v in w], torch.from_numpy(g["wl"]) * 1e-3, label="golden")
+    check.check(torch.from_numpy(got))
 
 
 def equal_and_black_case():
