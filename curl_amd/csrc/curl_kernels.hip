@@ -208,6 +208,7 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/psnr.inc"
 #include "kernels/msssim.inc"
 #include "kernels/poly_bwd.inc"
+#include "kernels/poly_layer_bwd.inc"
 #include "kernels/loss.inc"
 #include "kernels/edges.inc"
 #include "kernels/host_api.inc"

@@ -493,4 +493,65 @@ CURL_HD void coef_grad_expand_foldx(float (&e)[PolyFoldX<C>::kSlice], const fold
   foldx_expand<C, S>(e, a, xp);
 }
 
+// ---------------------------------------------------------------- backward of the stand-alone polynomial layer
+// ChannelPolyLayer(degree 4) / Deg4MobilePolyLayer on their own (model.py:295-333, 399-415): out[o] = P_o(v), the V variables
+// read straight from memory.  Two gradients:
+//   d coeffs[o][t] = sum_px g[o] * m_t(v)                     -- coef_grad_accumulate above, on the planes themselves
+//   d v[i]         = sum_o g[o] * dP_o/dv_i(v)                -- below
+// d m_t / d v_i = p_{t,i} * m_{t - e_i}, so dP_o/dv_i is a polynomial of degree 3 whose coefficient of monomial u is
+// (u_i + 1) * coef[o][idx(u + e_i)] (kPolyDerivIdx / kPolyDerivMul, poly_horner.inc): 3 V derivative polynomials of 20 (V = 3)
+// or 56 (V = 5) coefficients per image, formed once per workgroup and evaluated with the degree-3 Horner scheme -- 19 / 55
+// FMAs each, the lane's pixels in lock step as in the forward.  (Against the monomial form sum_u D[u] * m_u: the same FMA
+// count within 2 %, no 56 live monomials per pixel.)
+template <int V>
+struct PolyDeriv;
+template <>
+struct PolyDeriv<5> {
+  static constexpr int kTerms = 56;
+  template <class F, bool SEQ, int NP>
+  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][5], const float* c) { poly_d3_v5<F, SEQ, NP>(out, v, c); }
+  static CURL_HD int order(int pos) { return kPolyOrder_d3_v5[pos]; }
+  static CURL_HD int src(int i, int u) { return kPolyDerivIdx_d4_v5[i][u]; }
+  static CURL_HD float mul(int i, int u) { return (float)kPolyDerivMul_d4_v5[i][u]; }
+};
+template <>
+struct PolyDeriv<3> {
+  static constexpr int kTerms = 20;
+  template <class F, bool SEQ, int NP>
+  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][3], const float* c) { poly_d3_v3<F, SEQ, NP>(out, v, c); }
+  static CURL_HD int order(int pos) { return kPolyOrder_d3_v3[pos]; }
+  static CURL_HD int src(int i, int u) { return kPolyDerivIdx_d4_v3[i][u]; }
+  static CURL_HD float mul(int i, int u) { return (float)kPolyDerivMul_d4_v3[i][u]; }
+};
+// Entry j of an image's derivative table [V][3][kTerms], polynomial (i, o) in the order the degree-3 scheme consumes its
+// coefficients.  coef = [3][NC] of the image, reference order.  (kTerms is a multiple of 4: every polynomial starts on a
+// 16-byte boundary of the LDS copy.)
+template <int V>
+CURL_HD float poly_deriv_stage(const float* coef, int j) {
+  constexpr int NT = PolyDeriv<V>::kTerms, NC = PolyEval<V>::kCoeffs;
+  const int q = j / NT, pos = j - q * NT, i = q / 3, o = q - 3 * i;
+  const int u = PolyDeriv<V>::order(pos);
+  return PolyDeriv<V>::mul(i, u) * coef[o * NC + PolyDeriv<V>::src(i, u)];
+}
+// gin[i][e] = sum_o g[o][e] * dP_o/dv_i(vars[.][e]) for the N pixels of a lane; D = the image's poly_deriv_stage table.
+// Scalar chains (poly_fmav), N of them in lock step per coefficient read, as poly_layer_kernel evaluates the forward.
+template <int V, int N>
+CURL_HD void poly_img_grad_n(float (&gin)[V][N], const float (&vars)[V][N], const float (&g)[3][N], const float* D) {
+  constexpr int NT = PolyDeriv<V>::kTerms;
+  float vs[N][V], rs[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e)
+#pragma unroll
+    for (int k = 0; k < V; ++k) vs[e][k] = vars[k][e];
+#pragma unroll
+  for (int i = 0; i < V; ++i)
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+      CURL_FENCE();
+      PolyDeriv<V>::template eval<float, true, N>(rs, vs, D + (i * 3 + o) * NT);
+#pragma unroll
+      for (int e = 0; e < N; ++e) gin[i][e] = o == 0 ? g[0][e] * rs[e] : poly_fmav(g[o][e], rs[e], gin[i][e]);
+    }
+}
+
 }  // namespace curlm

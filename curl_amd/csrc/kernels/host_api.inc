@@ -532,6 +532,40 @@ static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, con
   return hipGetLastError();
 }
 
+// The stand-alone polynomial layer's coefficient gradient: a tile = 1024 * steps pixels (256 lanes x steps groups of 4),
+// steps = B * H * W / 2^20 held to [4, 16] -- enough pixels per lane to amortise the block reduction, enough tiles to fill
+// the device on a training-sized batch.  The same for the float4 and the scalar instantiation (the scratch size must not
+// depend on the pointers' alignment).
+static unsigned poly_bwd_steps(int B, size_t HW) {
+  const size_t p = HW * (size_t)B >> 20;
+  return (unsigned)(p < 4 ? 4 : (p > 16 ? 16 : p));
+}
+static size_t poly_bwd_tiles(int B, size_t HW) {
+  const size_t per = 1024u * (size_t)poly_bwd_steps(B, HW);
+  return (HW + per - 1) / per;
+}
+template <int V>
+static void launch_poly_layer_bwd(const float* img, const float* coeffs, const float* gout, float* gimg, float* gcoef,
+                                  float* partial, int B, size_t HW, hipStream_t s) {
+  constexpr int NC = PolyEval<V>::kCoeffs;
+  if (gcoef) {
+    const unsigned tiles = (unsigned)poly_bwd_tiles(B, HW);
+    PolyLayerGradArgs a{img, gout, partial, (unsigned)HW, (unsigned)((HW + 3) / 4), tiles, poly_bwd_steps(B, HW), (unsigned)B * tiles};
+    const dim3 grid((a.items + 7u) / 8u * 8u * PolyEval<V>::kChunks), block(256);
+    if (planes_vec4(HW, nullptr, CURL_MASK_NONE, img, gout)) hipLaunchKernelGGL((poly_layer_coef_grad_kernel<V, 4>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((poly_layer_coef_grad_kernel<V, 1>), grid, block, 0, s, a);
+    hipLaunchKernelGGL(trispace_coef_final_kernel, dim3((3 * NC + COEF_FINAL_OUTS - 1) / COEF_FINAL_OUTS, (unsigned)B), dim3(256),
+                       0, s, partial, gcoef, tiles, 3 * NC);
+  }
+  if (gimg) {
+    const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, img, gout, gimg);
+    const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
+    const dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
+    if (aligned) hipLaunchKernelGGL((poly_layer_img_grad_kernel<V, 4>), grid, block, 0, s, img, coeffs, gout, gimg, n);
+    else hipLaunchKernelGGL((poly_layer_img_grad_kernel<V, 1>), grid, block, 0, s, img, coeffs, gout, gimg, n);
+  }
+}
+
 // What the backward entry points share once their own knot arguments are checked: the remaining argument checks, before
 // any HIP call, then the knot prep -- unless CURL_F_WS_READY: the workspace is the one the forward filled for THESE knots
 // (the autograd nodes keep it), and the prep launch and its kernel boundary go (a fifth of a training-crop-batch backward).
@@ -667,7 +701,8 @@ extern "C" {
 //        prediction == target (CURLLoss) and the PSNR of equal images under a float mask follow the reference (DESIGN.md 3e.8-9)
 // 0.1.9: backward entry points of the stand-alone curve ops, converters and fused stages (curl_*_bwd_f32)
 // 0.1.10: curl_layer_pwl_bwd_f32, the fused layer's backward with the paper's piecewise-linear curves (CURL_F_PWL)
-int curl_version(void) { return 110; }
+// 0.1.11: curl_poly_layer_bwd_f32, the stand-alone polynomial layers' backward (image and coefficient gradients)
+int curl_version(void) { return 111; }
 
 const char* curl_last_error(void) { return g_err; }
 
@@ -1411,6 +1446,37 @@ int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* gr
                      ? launch_trispace_bwd<5>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream)
                      : launch_trispace_bwd<3>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "trispace backward kernels");
+  return 0;
+}
+
+size_t curl_poly_layer_bwd_scratch_bytes(int B, int H, int W, int num_variables) {
+  if (B <= 0 || H <= 0 || W <= 0 || (num_variables != 5 && num_variables != 3)) return 0;
+  const size_t HW = (size_t)H * W;
+  return (size_t)B * poly_bwd_tiles(B, HW) * 3 * (num_variables == 5 ? 126 : 35) * sizeof(float);
+}
+
+int curl_poly_layer_bwd_f32(const float* img, const float* coeffs, const float* grad_out, float* grad_img, float* grad_coeffs,
+                            void* scratch, size_t scratch_bytes, int B, int H, int W, int num_variables, unsigned flags,
+                            curl_stream_t stream) {
+  g_err[0] = 0;
+  if (int rc = check_img(img, grad_out, B, H, W)) return rc;
+  if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
+  if (!grad_img && !grad_coeffs) return fail(CURL_E_NULL, "grad_img and grad_coeffs are both NULL: nothing to compute");
+  if (num_variables != 5 && num_variables != 3) return fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)");
+  if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (flags must be 0)");
+  const size_t HW = (size_t)H * W;
+  if (grad_coeffs) {  // the tile partials; the image gradient alone needs no scratch
+    if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_poly_layer_bwd_scratch_bytes(B, H, W, num_variables))
+      return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_poly_layer_bwd_scratch_bytes");
+    // a 1-D grid of (image, tile, chunk) blocks
+    if ((uint64_t)B * poly_bwd_tiles(B, HW) * 3u + 64u > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
+  }
+  if (num_variables == 5)
+    launch_poly_layer_bwd<5>(img, coeffs, grad_out, grad_img, grad_coeffs, (float*)scratch, B, HW, (hipStream_t)stream);
+  else
+    launch_poly_layer_bwd<3>(img, coeffs, grad_out, grad_img, grad_coeffs, (float*)scratch, B, HW, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "poly_layer backward kernels");
   return 0;
 }
 

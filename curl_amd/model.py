@@ -335,11 +335,30 @@ class _TriSpaceFn(torch.autograd.Function):
         return None, ops.trispace_backward(img, coeffs, grad_out.contiguous(), ctx.residual_only), None
 
 
-def _no_grad_path(coeffs, who):
-    """The stand-alone polynomial layers are forward-only kernels; gradients flow through TriSpaceRegNet's fused path."""
-    if torch.is_grad_enabled() and coeffs.requires_grad:
-        raise NotImplementedError(f"curl_amd: {who} alone is forward-only; TriSpaceRegNet.forward / generate_residual "
-                                  "carry the backward (ops.trispace_backward). Use torch.no_grad() here.")
+class _PolyLayerFn(torch.autograd.Function):
+    """Autograd node of the stand-alone polynomial layers: forward = ops.poly_layer (the no-grad launch), backward =
+    ops.poly_layer_backward for the gradients that are needed (image, coefficients or both)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, img, coeffs):
+        ctx.save_for_backward(img, coeffs)
+        return ops.poly_layer(img, coeffs)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        img, coeffs = ctx.saved_tensors
+        return ops.poly_layer_backward(img, coeffs, grad_out.contiguous(), need_img_grad=ctx.needs_input_grad[0],
+                                       need_coeffs_grad=ctx.needs_input_grad[1])
+
+
+def _poly_layer(img, coeffs):
+    """ops.poly_layer, through the autograd node when a gradient can be asked for."""
+    if torch.is_grad_enabled() and (img.requires_grad or coeffs.requires_grad):
+        return _PolyLayerFn.apply(img, coeffs)
+    return ops.poly_layer(img, coeffs)
 
 
 class ChannelPolyLayer(nn.Module):
@@ -368,8 +387,7 @@ class ChannelPolyLayer(nn.Module):
         if self.degree != 4 or self.num_variables not in (3, 5) or self.num_out != 3:
             raise NotImplementedError("the HIP polynomial kernel is built for degree 4, 3 or 5 variables, 3 outputs "
                                       "(the configurations model.py:426,450 use)")
-        _no_grad_path(coeffs, "ChannelPolyLayer")
-        return ops.poly_layer(img, coeffs)
+        return _poly_layer(img, coeffs)
 
 
 class Deg4MobilePolyLayer(nn.Module):
@@ -381,14 +399,14 @@ class Deg4MobilePolyLayer(nn.Module):
         self.powers = nn.Parameter(torch.Tensor(_powers(4, 5)), requires_grad=False)
 
     def forward(self, img, coeffs):
-        _no_grad_path(coeffs, "Deg4MobilePolyLayer")
-        return ops.poly_layer(img, coeffs.reshape(img.shape[0], 3, self.num_coeffs))
+        return _poly_layer(img, coeffs.reshape(img.shape[0], 3, self.num_coeffs))
 
 
 class PolyRegNet(nn.Module):
     """model.py:418-436: encoder -> [B,3,35] coefficients -> sigmoid(ChannelPolyLayer(degree 4, 3 variables)(img)) * mask.
-    The polynomial layer is the HIP kernel (ops.poly_layer; forward only, like the reference's use of this class in
-    inference); the backbone is injectable as in TriSpaceRegNet (the reference downloads timm's efficientnetv2_rw_s)."""
+    The polynomial layer is the HIP kernel (ops.poly_layer) and trains through its backward (ops.poly_layer_backward: the
+    coefficient gradient only, the image is data); sigmoid and the mask product are stock torch.  The backbone is injectable
+    as in TriSpaceRegNet (the reference downloads timm's efficientnetv2_rw_s)."""
 
     def __init__(self, num_channels=3, polynomial_order=4, backbone=None, feature_width=1792):
         super().__init__()
@@ -404,9 +422,6 @@ class PolyRegNet(nn.Module):
 
     def forward(self, img, mask):
         coeffs = self.backbone(img).reshape(img.shape[0], self.num_channels, self.num_coeffs)
-        if torch.is_grad_enabled() and coeffs.requires_grad:
-            raise NotImplementedError("curl_amd: PolyRegNet is forward-only (the trainable polynomial model of this "
-                                      "path is TriSpaceRegNet); wrap the call in torch.no_grad()")
         return self.sigmoid(self.polylayer(img, coeffs)) * mask
 
 

@@ -98,7 +98,7 @@ def _one_device(fn):
 
 # keyword arguments that carry no tensor, or one whose device the body checks itself against the image's (`out`: _check_out,
 # `workspace`: curl_layer_backward); any other tensor passed by keyword takes the slow, fully checked path
-_PLAIN_KWARGS = frozenset(("flags", "return_workspace", "residual_only", "need_grad_img", "max_intensity", "window_size",
+_PLAIN_KWARGS = frozenset(("flags", "return_workspace", "residual_only", "need_grad_img", "need_img_grad", "need_coeffs_grad", "max_intensity", "window_size",
                            "want_L", "out", "workspace"))
 
 
@@ -760,11 +760,8 @@ def trispace_backward(img, coeffs, grad_out, residual_only=False):
     return g
 
 
-@_one_device
-def poly_layer(img, coeffs):
-    """ChannelPolyLayer(degree=4) / Deg4MobilePolyLayer forward (model.py:295-333, 399-415):
-    img [B,V,H,W] with V = 5 or 3, coeffs [B,3,126|35] -> [B,3,H,W]."""
-    lib = _lib.load()
+def _poly_layer_args(img, coeffs):
+    """The stand-alone polynomial layer's tensor checks: img float32 [B,3|5,H,W], coeffs [B,3,35|126]."""
     _need_device(img, "img")
     _need_device(coeffs, "coeffs")
     if img.dim() != 4 or img.shape[1] not in (3, 5) or img.dtype != torch.float32:
@@ -773,11 +770,48 @@ def poly_layer(img, coeffs):
     nc = 126 if V == 5 else 35
     if tuple(coeffs.shape) != (B, 3, nc):
         raise ValueError(f"coeffs must be [B={B},3,{nc}], got {tuple(coeffs.shape)}")
-    img, c = img.contiguous(), _coeffs32(coeffs, pairs=False)  # poly_layer_kernel reads scalars
+    return img.contiguous(), _coeffs32(coeffs, pairs=False)  # the poly_layer kernels read scalars
+
+
+@_one_device
+def poly_layer(img, coeffs):
+    """ChannelPolyLayer(degree=4) / Deg4MobilePolyLayer forward (model.py:295-333, 399-415):
+    img [B,V,H,W] with V = 5 or 3, coeffs [B,3,126|35] -> [B,3,H,W]."""
+    lib = _lib.load()
+    img, c = _poly_layer_args(img, coeffs)
+    B, V, H, W = img.shape
     out = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device)
     _lib.check(lib.curl_poly_layer_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, V, _stream(img)),
                "curl_poly_layer_f32")
     return out
+
+
+def poly_layer_bwd_tile(B, H, W):
+    """Pixels per tile of poly_layer_backward's coefficient-gradient pass (include/curl_hip.h: 1024 * steps)."""
+    return 1024 * min(max(B * H * W >> 20, 4), 16)
+
+
+@_one_device
+def poly_layer_backward(img, coeffs, grad_out, need_img_grad=True, need_coeffs_grad=True):
+    """Backward of poly_layer: grad_out [B,3,H,W] = d loss / d out -> (grad_img [B,V,H,W] | None, grad_coeffs [B,3,35|126] |
+    None).  A gradient that is not needed is neither computed nor stored (its kernels are not launched)."""
+    lib = _lib.load()
+    img, c = _poly_layer_args(img, coeffs)
+    B, V, H, W = img.shape
+    _need_device(grad_out, "grad_out")
+    if tuple(grad_out.shape) != (B, 3, H, W) or grad_out.dtype != torch.float32:
+        raise ValueError(f"grad_out must be float32 [B={B},3,{H},{W}], got {tuple(grad_out.shape)} {grad_out.dtype}")
+    if not need_img_grad and not need_coeffs_grad:
+        return None, None
+    grad_out = grad_out.contiguous()
+    g_img = torch.empty_like(img) if need_img_grad else None
+    g_c = torch.empty_like(c) if need_coeffs_grad else None
+    nbytes = lib.curl_poly_layer_bwd_scratch_bytes(B, H, W, V) if need_coeffs_grad else 0
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=img.device) if need_coeffs_grad else None
+    rc = lib.curl_poly_layer_bwd_f32(img.data_ptr(), c.data_ptr(), grad_out.data_ptr(), _ptr(g_img), _ptr(g_c), _ptr(scratch),
+                                     nbytes, B, H, W, V, 0, _stream(img))
+    _lib.check(rc, "curl_poly_layer_bwd_f32")
+    return g_img, g_c
 
 
 # ------------------------------------------------------------------ layout edges

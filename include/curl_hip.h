@@ -319,6 +319,23 @@ int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* gr
 int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B, int H, int W,
                         int num_variables, curl_stream_t stream);
 
+/* replaces: autograd of ChannelPolyLayer(degree=4).forward / Deg4MobilePolyLayer.forward  model.py:295-333, 399-415
+ * img [B,num_variables,H,W], coeffs [B,3,35|126], grad_out [B,3,H,W] (= d loss / d out of curl_poly_layer_f32) ->
+ *   grad_img    [B,num_variables,H,W]  ASSIGNED, or NULL: not wanted (the kernel that forms it is not launched);
+ *   grad_coeffs [B,3,35|126]           ASSIGNED, or NULL: not wanted (neither reduction pass is launched).
+ * At least one of the two must be given.  grad_img must not alias img, coeffs or grad_out.  num_variables 3 or 5 as in
+ * the forward; flags must be 0.
+ * grad_coeffs: one pass over img and grad_out, register-tiled outer products with the monomials, one row of partials per
+ * tile, fixed-order float64 sum (no atomics: a repeated call is bit-identical, and the result does not depend on the
+ * pointers' alignment).  grad_img: per pixel, the 3 * num_variables derivative polynomials (degree 3) of the image in LDS.
+ * scratch (16-byte aligned; used for grad_coeffs only -- with grad_coeffs == NULL it may be NULL):
+ *   curl_poly_layer_bwd_scratch_bytes = B * tiles * 3 * (35|126) * sizeof(float),
+ *   tiles = ceil(H*W / (1024 * steps)), steps = B*H*W / 2^20 (integer division) held to [4, 16];  0 on bad arguments. */
+size_t curl_poly_layer_bwd_scratch_bytes(int B, int H, int W, int num_variables);
+int curl_poly_layer_bwd_f32(const float* img, const float* coeffs, const float* grad_out, float* grad_img,
+                            float* grad_coeffs, void* scratch, size_t scratch_bytes, int B, int H, int W,
+                            int num_variables, unsigned flags, curl_stream_t stream);
+
 /* replaces: PIL + TF.to_tensor + transpose.swapimdims_HW3_3HW at the file edge
  *           infer.py:35-40, data.py:133-158, transpose.py:19-31
  * in: uint8 [B,H,W,Cin] with Cin = 3 or 4 (alpha dropped); out: float32 [B,3,H,W] = value/255. */

@@ -273,8 +273,35 @@ def gen_foldx(degree, nvars, chunk):
     return "\n".join(out).replace("\\n", "\n")
 
 
+def deriv_tables(degree, nvars):
+    """d m_t / d v_i = p_{t,i} * m_{t - e_i}: the derivative of the degree-`degree` polynomial by variable i is a polynomial of
+    degree - 1 whose coefficient of monomial u is (u_i + 1) * coef[idx(u + e_i)].  The order is graded, so the monomials u of
+    degree <= degree - 1 are the first len(powers(degree - 1)) entries of the same table.  Returns (idx, mul), each
+    [nvars][number of u]."""
+    full = {t: i for i, t in enumerate(powers(degree, nvars))}
+    small = powers(degree - 1, nvars)
+    assert small == powers(degree, nvars)[:len(small)]
+    idx = [[full[u[:i] + (u[i] + 1,) + u[i + 1:]] for u in small] for i in range(nvars)]
+    mul = [[u[i] + 1 for u in small] for i in range(nvars)]
+    return idx, mul
+
+
+def gen_deriv(degree, nvars):
+    """The tables of deriv_tables as arrays: the backward of the stand-alone polynomial layer stages
+    D[i][o][u] = kPolyDerivMul[i][u] * coef[o][kPolyDerivIdx[i][u]] and evaluates the derivative polynomials with the
+    degree-(degree - 1) Horner scheme above."""
+    idx, mul = deriv_tables(degree, nvars)
+    n = len(idx[0])
+    rows_i = ",\n  ".join("{" + ", ".join(str(x) for x in r) + "}" for r in idx)
+    rows_m = ",\n  ".join("{" + ", ".join(str(x) for x in r) + "}" for r in mul)
+    return (f"// d/dv_i of the degree-{degree}, {nvars}-variable polynomial: coefficient of monomial u (reference order, degree <= {degree - 1}:\n"
+            f"// the first {n} entries) = kPolyDerivMul[i][u] * coef[kPolyDerivIdx[i][u]]  (mul = u_i + 1, idx = index of u + e_i)\n"
+            f"constexpr unsigned short kPolyDerivIdx_d{degree}_v{nvars}[{nvars}][{n}] = {{\n  {rows_i}}};\n"
+            f"constexpr unsigned char kPolyDerivMul_d{degree}_v{nvars}[{nvars}][{n}] = {{\n  {rows_m}}};\n")
+
+
 def main():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    root =os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = os.path.join(root, "curl_amd", "csrc", "poly_horner.inc")
     parts = ["// GENERATED by tools/gen_poly_horner.py -- do not edit.\n"
              "// Multivariate Horner evaluators in the coefficient order of the reference's generate_powers\n"
@@ -293,6 +320,10 @@ def main():
     parts.append(gen_monomials(4, 3, 35))
     parts.append(gen_monomials(4, 4, 35))
     parts.append(gen_foldx(4, 5, 35))
+    # the stand-alone layer's image gradient: Horner schemes of the derivative polynomials (degree 3) and their coefficient maps
+    for nvars in (5, 3):
+        parts.append(gen(3, nvars)[1])
+        parts.append(gen_deriv(4, nvars))
     open(out, "w").write("\n".join(parts))
     print("wrote", out)
 
