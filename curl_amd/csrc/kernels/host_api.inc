@@ -26,28 +26,60 @@ static int check_flags(unsigned flags, unsigned allowed) {
     return fail(CURL_E_FLAGS, "curve-collapse placement must be 0 (library's choice), 1 (separate launch) or 2 (in the kernel)");
   return 0;
 }
-
-// float4 access to image planes: plane size a multiple of 4 pixels, every base 16-byte aligned (uint8 masks: 4-byte)
-static bool planes_vec4(size_t HW, const void* mask, int mask_kind, const void* p0, const void* p1 = nullptr,
-                        const void* p2 = nullptr, const void* p3 = nullptr) {
-  bool ok = (HW % 4 == 0) && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) % 16 == 0);
-  if (mask_kind == CURL_MASK_F32 && ((uintptr_t)mask % 16)) ok = false;
-  if (mask_kind == CURL_MASK_U8 && ((uintptr_t)mask % 4)) ok = false;
-  return ok;
+// the last HIP error as an entry point's return value (`where` names the kernels in curl_last_error)
+static int hip_done(const char* where) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, where) : 0;
 }
-// LAUNCH(VEC, MASK, ...) over (aligned, mask_kind); what follows mask_kind is handed on to LAUNCH
-#define DISPATCH_VEC_MASK(LAUNCH, aligned, mask_kind, ...)                            \
-  do {                                                                                \
-    if (aligned) {                                                                    \
-      if ((mask_kind) == CURL_MASK_U8) LAUNCH(4, CURL_MASK_U8, ##__VA_ARGS__);        \
-      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(4, CURL_MASK_F32, ##__VA_ARGS__); \
-      else LAUNCH(4, CURL_MASK_NONE, ##__VA_ARGS__);                                  \
-    } else {                                                                          \
-      if ((mask_kind) == CURL_MASK_U8) LAUNCH(1, CURL_MASK_U8, ##__VA_ARGS__);        \
-      else if ((mask_kind) == CURL_MASK_F32) LAUNCH(1, CURL_MASK_F32, ##__VA_ARGS__); \
-      else LAUNCH(1, CURL_MASK_NONE, ##__VA_ARGS__);                                  \
-    }                                                                                 \
-  } while (0)
+
+// every pointer on a grid of `bytes` (NULL is on every grid)
+template <class... P>
+static bool on_grid(unsigned bytes, const P*... p) {
+  return ((uintptr_t)0 | ... | (uintptr_t)p) % bytes == 0;
+}
+// THE float4-or-scalar verdict.  float4 access to image planes: plane size a multiple of 4 pixels, every image base on a grid
+// of base_align bytes -- 16 for float planes, 4 for the byte edges' interleaved images (dword accesses) --, float masks on the
+// 16-byte grid, uint8 masks on the 4-byte one (a mask pointer that mask_kind does not name is nobody's business)
+template <class... P>
+static bool planes_vec4(size_t HW, const void* mask, int mask_kind, unsigned base_align, const P*... bases) {
+  return HW % 4 == 0 && on_grid(base_align, bases...) && (mask_kind != CURL_MASK_F32 || on_grid(16, mask)) &&
+         (mask_kind != CURL_MASK_U8 || on_grid(4, mask));
+}
+// What a pointwise kernel outside the stream_kernel skeleton is launched with: one lane per float4 group (or pixel), 256-thread
+// blocks, grid (blocks per image, image)
+struct Pointwise {
+  bool aligned;
+  unsigned n, bpi;  // groups per plane, blocks per image
+  dim3 grid;
+  bool too_large() const { return (uint64_t)bpi * (uint64_t)grid.y > 0x7fffffffull; }  // (asked by the entries with partial rows per block)
+};
+static Pointwise pointwise(size_t HW, int B, bool aligned) {
+  Pointwise p;
+  p.aligned = aligned;
+  p.n = (unsigned)(HW / (aligned ? 4 : 1));
+  p.bpi = (p.n + 255u) / 256u;
+  p.grid = dim3(p.bpi, (unsigned)B);
+  return p;
+}
+// f(VEC, MK) with std::integral_constants for the vector width (4 or 1) and the mask kind, over (aligned, mask_kind); MASKS
+// names the mask kinds the kernel family is instantiated for, so that no other instantiation comes into being
+enum MaskKinds { kMasksAll, kMasksNone, kMasksU8F32 };
+template <int I>
+using int_c = std::integral_constant<int, I>;
+template <MaskKinds MASKS, class F>
+static void dispatch_vec_mask(bool aligned, int mask_kind, F&& f) {
+  const auto with_vec = [&](auto vec) {
+    if constexpr (MASKS == kMasksNone) {
+      f(vec, int_c<CURL_MASK_NONE>());
+    } else {
+      if (mask_kind == CURL_MASK_U8) f(vec, int_c<CURL_MASK_U8>());
+      else if (MASKS == kMasksU8F32 || mask_kind == CURL_MASK_F32) f(vec, int_c<CURL_MASK_F32>());
+      else if constexpr (MASKS == kMasksAll) f(vec, int_c<CURL_MASK_NONE>());
+    }
+  };
+  if (aligned) with_vec(int_c<4>());
+  else with_vec(int_c<1>());
+}
 
 constexpr unsigned kXcdDefault = 1;  // library default of the workgroup -> tile mapping: 1 = plain, 2 = XCD-contiguous
 struct Geometry {
@@ -59,21 +91,29 @@ struct Geometry {
   int nt;  // non-temporal loads and stores (float4 kernels)
   unsigned threads = 256;      // block size (row-tiled ops: follows the row width)
   unsigned units = 0, segs = 0;  // row-tiled ops: vec groups per row, blocks per row
-  unsigned lds_cap = 0;  // CURL_F_TUNE_OCC: unused dynamic LDS bytes per workgroup that hold the CU to k resident workgroups
+  unsigned lds_cap = 0;  // unused dynamic LDS bytes per workgroup that hold the CU to k resident workgroups
 };
-// Row-tiled ops (Op::kRowTiles): a block covers (part of) ONE image row.  Block size = the multiple of 64 lanes
-// (<= 256) that wastes the fewest lanes on the last block of a row, larger preferred: 1500 px = 375 float4 groups
-// -> 2 blocks of 192 lanes (2.3 % idle) rather than 256 + 119.
+// Row tiles: a block covers (part of) ONE image row.  Block size = the multiple of 64 lanes (<= 256) that wastes the fewest
+// lanes on the last block of a row, larger preferred: 1500 px = 375 float4 groups -> 2 blocks of 192 lanes (2.3 % idle)
+// rather than 256 + 119.
+struct RowBlocks {
+  unsigned threads, segs;
+};
+static RowBlocks row_blocks(unsigned units) {
+  unsigned best_t = 64, best_waste = ~0u;
+  for (unsigned t = 64; t <= 256; t += 64) {
+    unsigned segs = (units + t - 1) / t, waste = segs * t - units;
+    if (waste <= best_waste) best_waste = waste, best_t = t;
+  }
+  return RowBlocks{best_t, (units + best_t - 1) / best_t};
+}
+// Row-tiled ops (Op::kRowTiles): the grid of a geometry whose vector width and tuning are decided
 static int make_row_geometry(Geometry& g, int B, int H, int W) {
   if (g.vec == 4 && W % 4 != 0) g.vec = 1;  // rows must start on a float4 boundary
   g.units = (unsigned)(W / g.vec);
-  unsigned best_t = 64, best_waste = ~0u;
-  for (unsigned t = 64; t <= 256; t += 64) {
-    unsigned segs = (g.units + t - 1) / t, waste = segs * t - g.units;
-    if (waste <= best_waste) best_waste = waste, best_t = t;
-  }
-  g.threads = best_t;
-  g.segs = (g.units + best_t - 1) / best_t;
+  const RowBlocks rb = row_blocks(g.units);
+  g.threads = rb.threads;
+  g.segs = rb.segs;
   g.n = (unsigned)((size_t)H * W / g.vec);
   uint64_t per_image = (uint64_t)g.segs * (uint64_t)H;
   if (per_image * (uint64_t)B > 0x7fffffffull || per_image > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
@@ -114,39 +154,53 @@ static unsigned aux_lds(unsigned k_resident, const dim3& grid, bool float4_path,
   return (k_resident > 1 && float4_path && (uint64_t)grid.x * grid.y >= kResidentMinTiles) ? lds_for_resident(k_resident, static_bytes) : 0u;
 }
 
-static int make_geometry(Geometry& g, const void* p0, const void* p1, const void* pm, int mask_kind, int B, int H, int W,
-                         unsigned flags, int default_unroll, size_t also_multiple_of_4 = 0) {
-  size_t HW = (size_t)H * W;
-  bool aligned = (HW % 4 == 0) && (also_multiple_of_4 % 4 == 0) && (((uintptr_t)p0 | (uintptr_t)p1) % 16 == 0);
-  if (pm && mask_kind == CURL_MASK_F32 && ((uintptr_t)pm % 16)) aligned = false;
-  if (pm && mask_kind == CURL_MASK_U8 && ((uintptr_t)pm % 4)) aligned = false;
-  g.vec = aligned ? 4 : 1;
-  int u = (int)((flags & CURL_F_TUNE_UNROLL_MASK) >> CURL_F_TUNE_UNROLL_SHIFT);
-  if (u == 0) u = default_unroll;
-  if (u != 1 && u != 2 && u != 4) return fail(CURL_E_FLAGS, "tuning unroll must be 1, 2 or 4");
-  g.unroll = u;
-  g.n = (unsigned)(HW / g.vec);
+// a launch's workgroups at one group per lane (256 lanes; 1024-pixel tiles on the float4 path): what the self-prep and residency rules count
+static uint64_t tiles_of(size_t groups, int B) { return (uint64_t)((groups + 255u) / 256u) * (uint64_t)B; }
+
+// The caller's tuning fields, parsed and validated: what of the launch's shape the flags ask for.  unroll = 0: no request
+// (ignore_unroll: ops built for one tile shape do not look at the field at all).
+struct Tuning {  // (as declared: nothing asked)
+  int unroll = 0;
+  unsigned threads = 256;  // block size
+  bool xcd = kXcdDefault == 2, nt = true;
+  bool shape_asked = false;  // a tile-shape or occupancy field is set (unroll, block size, occupancy)
+  unsigned lds_cap = 0;  // CURL_F_TUNE_OCC: k workgroups per CU (= k waves per SIMD at 256 threads), by an LDS reservation nobody uses
+};
+static int parse_tuning(Tuning& t, unsigned flags, bool ignore_unroll = false) {
+  t.unroll = ignore_unroll ? 0 : (int)((flags & CURL_F_TUNE_UNROLL_MASK) >> CURL_F_TUNE_UNROLL_SHIFT);
+  if (t.unroll != 0 && t.unroll != 1 && t.unroll != 2 && t.unroll != 4) return fail(CURL_E_FLAGS, "tuning unroll must be 1, 2 or 4");
   const unsigned bsel = (flags & CURL_F_TUNE_BLOCK_MASK) >> CURL_F_TUNE_BLOCK_SHIFT;
   if (bsel > 2) return fail(CURL_E_FLAGS, "tuning block size must be 0 (256), 1 (128) or 2 (64 threads)");
-  g.threads = 256u >> bsel;
-  unsigned per_chunk = g.threads * (unsigned)u;
+  t.threads = 256u >> bsel;
+  const unsigned xsel = (flags & CURL_F_TUNE_XCD_MASK) >> CURL_F_TUNE_XCD_SHIFT;
+  if (xsel > 2) return fail(CURL_E_FLAGS, "tuning tile mapping must be 0 (default), 1 (plain) or 2 (XCD-contiguous)");
+  t.xcd = (xsel ? xsel : kXcdDefault) == 2;
+  t.nt = !(flags & CURL_F_TUNE_NO_NT);
+  const unsigned occ = (flags & CURL_F_TUNE_OCC_MASK) >> CURL_F_TUNE_OCC_SHIFT;
+  t.lds_cap = occ > 1 ? lds_for_resident(occ) : 0u;  // occ == 1: "no cap" said explicitly (the operators' defaults off)
+  t.shape_asked = t.unroll || bsel || occ;
+  return 0;
+}
+// The grid arithmetic, last: `unroll` groups of `vec` floats per lane are decided, so is the LDS reservation
+static int make_geometry(Geometry& g, const Tuning& t, int vec, int unroll, unsigned lds_cap, size_t HW, int B) {
+  g.vec = vec;
+  g.unroll = unroll;
+  g.n = (unsigned)(HW / vec);
+  g.threads = t.threads;
+  const unsigned per_chunk = g.threads * (unsigned)unroll;
   g.blocks_per_image = (g.n + per_chunk - 1) / per_chunk;
-  uint64_t nb = (uint64_t)g.blocks_per_image * (uint64_t)B;
+  const uint64_t nb = (uint64_t)g.blocks_per_image * (uint64_t)B;
   if (nb > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
   g.n_blocks = (unsigned)nb;
-  g.nt = (flags & CURL_F_TUNE_NO_NT) ? 0 : 1;
   g.n_images = (unsigned)B;
-  unsigned xsel = (flags & CURL_F_TUNE_XCD_MASK) >> CURL_F_TUNE_XCD_SHIFT;
-  if (xsel > 2) return fail(CURL_E_FLAGS, "tuning tile mapping must be 0 (default), 1 (plain) or 2 (XCD-contiguous)");
-  g.xcd = (xsel ? xsel : kXcdDefault) == 2;
-  // CURL_F_TUNE_OCC: k workgroups per CU (= k waves per SIMD at 256 threads), by an LDS reservation nobody uses
-  const unsigned occ = (flags & CURL_F_TUNE_OCC_MASK) >> CURL_F_TUNE_OCC_SHIFT;
-  g.lds_cap = occ > 1 ? lds_for_resident(occ) : 0u;  // occ == 1: "no cap" said explicitly (launch_stream's default off)
+  g.nt = t.nt;
+  g.xcd = t.xcd;
+  g.lds_cap = lds_cap;
   return 0;
 }
 
 template <class Op, int VEC, int MK, bool NT>
-static hipError_t launch_u(const Geometry& g, const StreamArgs& a, hipStream_t s) {
+static void launch_u(const Geometry& g, const StreamArgs& a, hipStream_t s) {
   dim3 grid(a.xcd_per ? 8u * a.xcd_per : g.blocks_per_image, g.n_images), block(g.threads);
   if constexpr (Op::kSingleTileShape) {
     // very large ops (polynomial layers) are built for one tile shape only
@@ -170,35 +224,11 @@ static hipError_t launch_u(const Geometry& g, const StreamArgs& a, hipStream_t s
         break;
     }
   }
-  return hipGetLastError();
 }
 
-template <class Op, int MK>
-static hipError_t launch_v(const Geometry& g, const StreamArgs& a, hipStream_t s) {
-  if (g.vec == 4) return g.nt ? launch_u<Op, 4, MK, true>(g, a, s) : launch_u<Op, 4, MK, false>(g, a, s);
-  return launch_u<Op, 1, MK, false>(g, a, s);  // scalar correctness path: plain accesses
-}
-
-static PrepArgs make_prep(const float* r0, int n0, int K0, const float* r1, int n1, int K1, const float* r2, int n2, int K2,
-                          float* ws, unsigned stride, float* reg) {
-  PrepArgs p;
-  p.raw[0] = r0, p.raw[1] = r1, p.raw[2] = r2;
-  p.ncurves[0] = n0, p.ncurves[1] = n1, p.ncurves[2] = n2;
-  p.K[0] = K0, p.K[1] = K1, p.K[2] = K2;
-  p.ws = ws;
-  p.reg_out = reg;
-  p.stride = stride;
-  return p;
-}
 static int launch_prep(const PrepArgs& p, int B, hipStream_t s) {
   hipLaunchKernelGGL(knots_prep_kernel, dim3(B), dim3(256), 0, s, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "knots_prep_kernel");
-  return 0;
-}
-static int run_prep(const float* r0, int n0, int K0, const float* r1, int n1, int K1, const float* r2, int n2, int K2,
-                    float* ws, unsigned stride, float* reg, int B, hipStream_t s) {
-  return launch_prep(make_prep(r0, n0, K0, r1, n1, K1, r2, n2, K2, ws, stride, reg), B, s);
+  return hip_done("knots_prep_kernel");
 }
 
 // rows [row0, row0 + rows) of images that are H_full rows high; H_full == 0: whole images
@@ -213,71 +243,51 @@ struct Slab {
 // 19.3): tools/small_batch.py, profiles/r04/small_batch_*.log.
 constexpr unsigned kSelfPrepMaxTiles = 2048u;
 
-template <class Op, int MK>
-static hipError_t launch_selfprep(const Geometry& g, const StreamArgs& a, const PrepArgs& p, hipStream_t s) {
-  dim3 grid(g.blocks_per_image, g.n_images), block(256);
-  if (g.vec == 4) hipLaunchKernelGGL((stream_selfprep_kernel<Op, 4, MK, true>), grid, block, 0, s, a, p);
-  else hipLaunchKernelGGL((stream_selfprep_kernel<Op, 1, MK, false>), grid, block, 0, s, a, p);
-  return hipGetLastError();
-}
-
 // prep: the call's curve collapse, not yet launched (NULL: the op needs none, or the workspace is ready) -- launch_stream
-// decides between a launch of its own and the in-kernel form (CURL_F_TUNE_PREP)
+// decides between a launch of its own and the in-kernel form (CURL_F_TUNE_PREP).  Every decision is taken once, in this
+// order, and every check is through before the first launch: the float4-or-scalar verdict (pointers, sizes and the slab
+// only), the caller's tuning fields, the groups per lane and the LDS reservation, the grid.
 template <class Op>
 static int launch_stream(const float* in, float* out, const void* mask, int mask_kind, const float* coef,
                          unsigned coef_stride, int B, int H, int W, unsigned flags, hipStream_t s, const char* name,
                          int op_flag = 0, Slab slab = Slab(), const PrepArgs* prep = nullptr) {
-  Geometry g;
-  bool self_prep = false;
-  if (prep) {
-    if constexpr (Op::kSelfPrep) {
-      const unsigned psel = (flags & CURL_F_TUNE_PREP_MASK) >> CURL_F_TUNE_PREP_SHIFT;
-      const unsigned shape = CURL_F_TUNE_UNROLL_MASK | CURL_F_TUNE_BLOCK_MASK | CURL_F_TUNE_XCD_MASK | CURL_F_TUNE_OCC_MASK |
-                             CURL_F_TUNE_NO_NT | CURL_F_DIAG_NO_MEM | CURL_F_MASK_FIRST;
-      // the grid the geometry below will produce at one group per lane: 1024-pixel workgroups on the float4 path, 256-pixel
-      // ones on the scalar path (H*W or a pointer off the float4 grid -- 32 crops of 255x255 are 8 160 workgroups, not 2 048:
-      // no longer resident at once, each paying the prologue; ADVICE r4).  Same test as make_geometry's.
-      Geometry probe;
-      const size_t ppx = slab.H_full ? (size_t)slab.H_full * W : (size_t)H * W;
-      if (int rc = make_geometry(probe, in, out, mask, mask_kind, B, H, W, 1u << CURL_F_TUNE_UNROLL_SHIFT, 1, ppx | (size_t)slab.row0 * W))
-        return rc;
-      self_prep = !(flags & shape) && !Op::kMaskFirst && (psel == 2 || (psel == 0 && probe.n_blocks <= kSelfPrepMaxTiles));
-    }
-    if (!self_prep)
-      if (int rc = launch_prep(*prep, B, s)) return rc;
-  }
-  flags &= ~CURL_F_TUNE_PREP_MASK;
-  if (self_prep) flags |= 1u << CURL_F_TUNE_UNROLL_SHIFT;  // one group per lane
-
-  if (Op::kSingleTileShape) flags &= ~CURL_F_TUNE_UNROLL_MASK;
   // a slab's plane stride and first-row offset must be float4 multiples too for the vector kernels (else scalar)
-  const size_t plane_px = slab.H_full ? (size_t)slab.H_full * W : (size_t)H * W, off_px = (size_t)slab.row0 * W;
-  if (int rc = make_geometry(g, in, out, mask, mask_kind, B, H, W, flags, Op::kUnroll, plane_px | off_px)) return rc;
+  const size_t HW = (size_t)H * W, plane_px = slab.H_full ? (size_t)slab.H_full * W : HW, off_px = (size_t)slab.row0 * W;
+  const int vec = planes_vec4(HW, mask, mask_kind, 16, in, out) && (plane_px | off_px) % 4 == 0 ? 4 : 1;
+  Tuning t;
+  if (int rc = parse_tuning(t, flags, Op::kSingleTileShape)) return rc;
+  const bool no_mem = flags & CURL_F_DIAG_NO_MEM, mask_first = !no_mem && (Op::kMaskFirst || (flags & CURL_F_MASK_FIRST));
+  // the launch's workgroups at one group per lane: 1024-pixel ones on the float4 path, 256-pixel ones on the scalar path (H*W
+  // or a pointer off the float4 grid -- 32 crops of 255x255 are 8 160 workgroups, not 2 048: no longer resident at once, each
+  // paying the prologue; ADVICE r4)
+  const uint64_t tiles = tiles_of(HW / vec, B);
+  int unroll = t.unroll ? t.unroll : Op::kUnroll;
+  unsigned lds_cap = t.lds_cap;
+  bool self_prep = false;
+  if constexpr (Op::kSelfPrep) {
+    const unsigned psel = (flags & CURL_F_TUNE_PREP_MASK) >> CURL_F_TUNE_PREP_SHIFT;
+    const bool as_is = !t.shape_asked && !(flags & (CURL_F_TUNE_XCD_MASK | CURL_F_TUNE_NO_NT | CURL_F_MASK_FIRST)) && !no_mem;
+    if (prep && tiles > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");  // (the in-kernel form's grid, whichever form runs)
+    self_prep = prep && as_is && !Op::kMaskFirst && (psel == 2 || (psel == 0 && tiles <= kSelfPrepMaxTiles));
+    if (self_prep) unroll = 1;  // one group per lane
+  }
   if constexpr (Op::kResident > 0) {
     // large float4 launches with no tile-shape / occupancy request of the caller's: one group per lane, Op::kResident
     // workgroups per CU (ops.inc OpDefaults::kResident)
-    const unsigned tune = CURL_F_TUNE_UNROLL_MASK | CURL_F_TUNE_BLOCK_MASK | CURL_F_TUNE_OCC_MASK;
-    if (!(flags & tune) && g.vec == 4 && (uint64_t)((g.n + 255u) / 256u) * (uint64_t)B >= kResidentMinTiles) {
-      if (int rc = make_geometry(g, in, out, mask, mask_kind, B, H, W, flags | (1u << CURL_F_TUNE_UNROLL_SHIFT), 1, plane_px | off_px))
-        return rc;
-      g.lds_cap = lds_for_resident(Op::kResident);
-    }
+    if (!t.shape_asked && !self_prep && vec == 4 && tiles >= kResidentMinTiles) unroll = 1, lds_cap = lds_for_resident(Op::kResident);
   }
   // the mask-first kernel variant exists at one group per lane: a caller who asks for it gets that tile shape (ops whose
   // default is two groups -- the HSV stage below kResidentMinTiles -- would otherwise ignore the flag silently; ADVICE r3)
-  if constexpr (Op::kMask && !Op::kSingleTileShape) {
-    const bool want = (Op::kMaskFirst || (flags & CURL_F_MASK_FIRST)) && mask_kind == CURL_MASK_U8 && !(flags & CURL_F_DIAG_NO_MEM);
-    if (want && g.vec == 4 && g.unroll != 1 && !(flags & CURL_F_TUNE_UNROLL_MASK)) {
-      const unsigned cap = g.lds_cap;
-      if (int rc = make_geometry(g, in, out, mask, mask_kind, B, H, W, flags | (1u << CURL_F_TUNE_UNROLL_SHIFT), 1, plane_px | off_px))
-        return rc;
-      g.lds_cap = cap;
-    }
-  }
-  if constexpr (Op::kLdsFloats > 0 || Op::kRowTiles) g.lds_cap = 0;  // ops with LDS tables of their own: no reservation on top
+  if constexpr (Op::kMask && !Op::kSingleTileShape)
+    if (mask_first && mask_kind == CURL_MASK_U8 && vec == 4 && !t.unroll) unroll = 1;
+  if constexpr (Op::kLdsFloats > 0 || Op::kRowTiles) lds_cap = 0;  // ops with LDS tables of their own: no reservation on top
+  Geometry g;
+  if (int rc = make_geometry(g, t, vec, unroll, lds_cap, HW, B)) return rc;
   if constexpr (Op::kRowTiles)
     if (int rc = make_row_geometry(g, B, H, W)) return rc;
   if (plane_px % g.vec || off_px % g.vec) return fail(CURL_E_SHAPE, "internal: slab not aligned to the vector width");
+  if (prep && !self_prep)
+    if (int rc = launch_prep(*prep, B, s)) return rc;
   StreamArgs a;
   a.in = in;
   a.out = out;
@@ -287,68 +297,42 @@ static int launch_stream(const float* in, float* out, const void* mask, int mask
   a.n = g.n;
   a.blocks_per_image = g.blocks_per_image;
   a.n_blocks = g.n_blocks;
-  a.no_mem = (flags & CURL_F_DIAG_NO_MEM) ? 1 : 0;
+  a.no_mem = no_mem;
   a.W = (unsigned)W;
   a.H = (unsigned)(slab.H_full ? slab.H_full : H);
   a.op_flag = op_flag;
-  a.mask_first = (flags & CURL_F_DIAG_NO_MEM) ? 0 : (Op::kMaskFirst || (flags & CURL_F_MASK_FIRST)) ? 1 : 0;
+  a.mask_first = mask_first;
   a.white = nullptr;
   a.units = g.units, a.segs = g.segs;
   a.plane = (unsigned)(plane_px / g.vec), a.off = (unsigned)(off_px / g.vec), a.row0 = (unsigned)slab.row0;
   a.xcd_per = (g.xcd && !Op::kRowTiles && g.blocks_per_image >= 64u) ? (g.blocks_per_image + 7u) / 8u : 0u;
-  hipError_t e;
-  if constexpr (Op::kSelfPrep) {
-    if (self_prep) {
-      if constexpr (Op::kMask) {
-        e = (mask_kind == CURL_MASK_U8)    ? launch_selfprep<Op, CURL_MASK_U8>(g, a, *prep, s)
-            : (mask_kind == CURL_MASK_F32) ? launch_selfprep<Op, CURL_MASK_F32>(g, a, *prep, s)
-                                           : launch_selfprep<Op, CURL_MASK_NONE>(g, a, *prep, s);
-      } else {
-        e = launch_selfprep<Op, CURL_MASK_NONE>(g, a, *prep, s);
+  dispatch_vec_mask<Op::kMask ? kMasksAll : kMasksNone>(g.vec == 4, mask_kind, [&](auto V, auto M) {
+    constexpr bool kNT = V == 4;  // the scalar correctness path: plain accesses
+    if constexpr (Op::kSelfPrep) {
+      if (self_prep) {
+        hipLaunchKernelGGL((stream_selfprep_kernel<Op, V, M, kNT>), dim3(g.blocks_per_image, g.n_images), dim3(256), 0, s, a, *prep);
+        return;
       }
-      if (e != hipSuccess) return hip_fail(e, name);
-      return 0;
     }
-  }
-  if constexpr (Op::kMask) {
-    e = (mask_kind == CURL_MASK_U8)    ? launch_v<Op, CURL_MASK_U8>(g, a, s)
-        : (mask_kind == CURL_MASK_F32) ? launch_v<Op, CURL_MASK_F32>(g, a, s)
-                                       : launch_v<Op, CURL_MASK_NONE>(g, a, s);
-  } else {
-    e = launch_v<Op, CURL_MASK_NONE>(g, a, s);
-  }
-  if (e != hipSuccess) return hip_fail(e, name);
-  return 0;
+    if (kNT && !g.nt) launch_u<Op, V, M, false>(g, a, s);
+    else launch_u<Op, V, M, kNT>(g, a, s);
+  });
+  return hip_done(name);
 }
 
-// FMT_U8HWC launch: interleaved bytes in and out, optional white-background mask; one tile shape per op
-template <class Op, int MK>
-static hipError_t launch_u8_v(const Geometry& g, const StreamArgs& a, hipStream_t s) {
-  dim3 grid(g.blocks_per_image, g.n_images), block(g.threads);
-  constexpr int U = Op::kSingleTileShape ? 1 : Op::kUnroll;
-  if (g.vec == 4)
-    hipLaunchKernelGGL((stream_kernel<Op, 4, U, MK, true, FMT_U8HWC>), grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL((stream_kernel<Op, 1, U, MK, false, FMT_U8HWC>), grid, block, 0, s, a);
-  return hipGetLastError();
-}
+// FMT_U8HWC launch: interleaved bytes in and out, optional white-background mask; one tile shape per op, no tuning
 template <class Op>
 static int launch_stream_u8(const uint8_t* in, uint8_t* out, const void* mask, int mask_kind, const uint8_t* white,
                             const float* coef, unsigned coef_stride, int B, int H, int W, hipStream_t s,
-                            const char* name, int op_flag = 0) {
+                            const char* name, const PrepArgs* prep = nullptr) {
+  constexpr int U = Op::kSingleTileShape ? 1 : Op::kUnroll;
+  const size_t HW = (size_t)H * W;
   Geometry g;
-  if (int rc = make_geometry(g, in, out, mask, mask_kind, B, H, W, 0, Op::kSingleTileShape ? 1 : Op::kUnroll)) return rc;
-  // make_geometry asks 16-byte alignment of in/out for the vector path; dword accesses need 4 (also for `white`)
-  size_t HW = (size_t)H * W;
-  bool aligned = (HW % 4 == 0) && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)white) % 4 == 0);
-  if (mask && mask_kind == CURL_MASK_F32 && ((uintptr_t)mask % 16)) aligned = false;
-  if (mask && mask_kind == CURL_MASK_U8 && ((uintptr_t)mask % 4)) aligned = false;
-  g.vec = aligned ? 4 : 1;
-  g.n = (unsigned)(HW / g.vec);
-  unsigned per_chunk = 256u * (unsigned)g.unroll;
-  g.blocks_per_image = (g.n + per_chunk - 1) / per_chunk;
+  if (int rc = make_geometry(g, Tuning(), planes_vec4(HW, mask, mask_kind, 4, in, out, white) ? 4 : 1, U, 0, HW, B)) return rc;
   if constexpr (Op::kRowTiles)
     if (int rc = make_row_geometry(g, B, H, W)) return rc;
+  if (prep)  // (always a launch of its own: the byte edge has no in-kernel collapse)
+    if (int rc = launch_prep(*prep, B, s)) return rc;
   StreamArgs a{};
   a.in = reinterpret_cast<const float*>(in);
   a.out = reinterpret_cast<float*>(out);
@@ -358,23 +342,18 @@ static int launch_stream_u8(const uint8_t* in, uint8_t* out, const void* mask, i
   a.coef_stride = coef_stride;
   a.n = g.n;
   a.blocks_per_image = g.blocks_per_image;
-  a.n_blocks = g.blocks_per_image * (unsigned)B;
+  a.n_blocks = g.n_blocks;
   a.no_mem = 0;
   a.W = (unsigned)W;
   a.H = (unsigned)H;
-  a.op_flag = op_flag;
+  a.op_flag = 0;
   a.units = g.units, a.segs = g.segs;
   a.plane = a.n, a.off = 0, a.row0 = 0;
-  hipError_t e;
-  if constexpr (Op::kMask) {
-    e = (mask_kind == CURL_MASK_U8)    ? launch_u8_v<Op, CURL_MASK_U8>(g, a, s)
-        : (mask_kind == CURL_MASK_F32) ? launch_u8_v<Op, CURL_MASK_F32>(g, a, s)
-                                       : launch_u8_v<Op, CURL_MASK_NONE>(g, a, s);
-  } else {
-    e = launch_u8_v<Op, CURL_MASK_NONE>(g, a, s);
-  }
-  if (e != hipSuccess) return hip_fail(e, name);
-  return 0;
+  const dim3 grid(g.blocks_per_image, g.n_images), block(g.threads);
+  dispatch_vec_mask<Op::kMask ? kMasksAll : kMasksNone>(g.vec == 4, mask_kind, [&](auto V, auto M) {
+    hipLaunchKernelGGL((stream_kernel<Op, V, U, M, V == 4, FMT_U8HWC>), grid, block, 0, s, a);
+  });
+  return hip_done(name);
 }
 
 static int check_mask(const void* mask, int mask_kind) {
@@ -393,49 +372,71 @@ static int check_K(int Kp, bool uneven_ok = false) {
 }
 static int check_ws(const void* ws, size_t bytes, int B, int n_knots) {
   if (!ws) return fail(CURL_E_WORKSPACE, "workspace is NULL");
-  if ((uintptr_t)ws % 16) return fail(CURL_E_WORKSPACE, "workspace must be 16-byte aligned");
+  if (!on_grid(16, ws)) return fail(CURL_E_WORKSPACE, "workspace must be 16-byte aligned");
   if (bytes < curl_workspace_bytes(B, n_knots)) return fail(CURL_E_WORKSPACE, "workspace too small");
   return 0;
 }
-// the fused layer's three knot segments: L and R of 3 curves, H of 4
-static int check_layer_knots(const float* rawL, const float* rawR, const float* rawH, int Kl, int Kr, int Kh, bool uneven_ok) {
+// The knot set-up of a call: knots checked, workspace checked, and what the curve collapse is launched with.  One segment of
+// n curves (adjust_*, the stages: 3 or 4) or the fused layer's three (L and R of 3 curves, H of 4).
+struct KnotSetup {
+  float* ws;
+  unsigned stride;
+  int n_knots;
+  PrepArgs prep;
+};
+static int knot_setup(KnotSetup& k, int segs, const float* const (&raw)[3], const int (&ncurves)[3], const int (&K)[3], bool uneven_ok,
+                      void* workspace, size_t workspace_bytes, int B, float* reg) {
+  k.n_knots = 0;
+  for (int i = 0; i < segs; ++i) {
+    if (int rc = check_K(K[i], uneven_ok)) return rc;
+    k.n_knots += KP_TOTAL(K[i], ncurves[i]);
+  }
+  if (int rc = check_ws(workspace, workspace_bytes, B, k.n_knots)) return rc;
+  k.ws = (float*)workspace;
+  k.stride = ws_stride(k.n_knots);
+  for (int i = 0; i < 3; ++i) k.prep.raw[i] = i < segs ? raw[i] : nullptr, k.prep.ncurves[i] = i < segs ? ncurves[i] : 0, k.prep.K[i] = i < segs ? K[i] : 0;
+  k.prep.ws = k.ws;
+  k.prep.reg_out = reg;
+  k.prep.stride = k.stride;
+  return 0;
+}
+static int segment_knots(KnotSetup& k, const float* raw, int n_curves, int K, bool uneven_ok, void* workspace, size_t workspace_bytes,
+                         int B, float* reg) {
+  return knot_setup(k, 1, {raw, nullptr, nullptr}, {n_curves, 0, 0}, {K, 0, 0}, uneven_ok, workspace, workspace_bytes, B, reg);
+}
+static int layer_knots(KnotSetup& k, const float* rawL, const float* rawR, const float* rawH, int Kl, int Kr, int Kh, bool uneven_ok,
+                       void* workspace, size_t workspace_bytes, int B, float* reg) {
   if (!rawL || !rawR || !rawH) return fail(CURL_E_NULL, "rawL/rawR/rawH must all be non-NULL");
-  if (int rc = check_K(Kl, uneven_ok)) return rc;
-  if (int rc = check_K(Kr, uneven_ok)) return rc;
-  return check_K(Kh, uneven_ok);
+  return knot_setup(k, 3, {rawL, rawR, rawH}, {3, 3, 4}, {Kl, Kr, Kh}, uneven_ok, workspace, workspace_bytes, B, reg);
 }
 static int layer_n_knots(int Kl, int Kr, int Kh) { return KP_TOTAL(Kl, 3) + KP_TOTAL(Kr, 3) + KP_TOTAL(Kh, 4); }
-
-template <int VEC>
-static hipError_t launch_chain_u(const Geometry& g, const ChainArgs& a, hipStream_t s) {
-  dim3 grid(g.blocks_per_image, g.n_images), block(g.threads);
-  switch (g.unroll) {
-    case 1:
-      hipLaunchKernelGGL((chain_kernel<VEC, 1>), grid, block, g.lds_cap, s, a);
-      break;
-    case 2:
-      hipLaunchKernelGGL((chain_kernel<VEC, 2>), grid, block, g.lds_cap, s, a);
-      break;
-    default:
-      hipLaunchKernelGGL((chain_kernel<VEC, 4>), grid, block, g.lds_cap, s, a);
-      break;
-  }
-  return hipGetLastError();
+// scratch buffers: present, large enough, and on the 16-byte grid where the kernels read them as float4 / double2
+static int check_scratch(const void* scratch, size_t bytes, size_t need, bool wants_16_byte_alignment, const char* msg) {
+  if (!scratch || (wants_16_byte_alignment && !on_grid(16, scratch)) || bytes < need) return fail(CURL_E_WORKSPACE, msg);
+  return 0;
+}
+static int check_num_coeffs(int num_coeffs, const char* msg) { return (num_coeffs != 126 && num_coeffs != 35) ? fail(CURL_E_KNOTS, msg) : 0; }
+static int check_num_variables(int num_variables) {
+  return (num_variables != 5 && num_variables != 3) ? fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)") : 0;
 }
 
-static int launch_chain(const float* in, float* out, const float* knots, unsigned knot_stride, int n_steps, int K,
-                        const int* knot_off, const int* cin, const int* cout, int mode, int B, int H, int W,
-                        unsigned flags, hipStream_t s) {
-  Geometry g;
-  if (int rc = make_geometry(g, in, out, nullptr, 0, B, H, W, flags & ~CURL_F_TUNE_BLOCK_MASK, 2)) return rc;  // 256-thread kernel
+// chain_kernel's launch in two steps, so that a caller's own launches (the knot prep, apply_curve's regulariser) come after
+// every check: the plan (verdict, tuning fields, groups per lane and LDS reservation, grid), then the launch
+static int plan_chain(Geometry& g, const float* in, const float* out, int mode, int B, int H, int W, unsigned flags) {
+  const size_t HW = (size_t)H * W;
+  const int vec = planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, in, out) ? 4 : 1;
+  Tuning t;
+  if (int rc = parse_tuning(t, flags & ~CURL_F_TUNE_BLOCK_MASK)) return rc;  // 256-thread kernel
+  int unroll = t.unroll ? t.unroll : 2;
+  unsigned lds_cap = t.lds_cap;
   // the affine form is a light streaming op (its block prologue -- knots to LDS, a barrier -- wants more waves than the
   // skeleton's ops: 5 workgroups per CU -- what round 3's nominal "7" was with the static tables counted --, one group per lane: 195.0 -> 186.9 us; profiles/r03/exp27j_occ_sweep_true_residency.log)
-  if (mode == 0 && !(flags & (CURL_F_TUNE_UNROLL_MASK | CURL_F_TUNE_OCC_MASK)) && g.vec == 4 &&
-      (uint64_t)((g.n + 255u) / 256u) * (uint64_t)B >= kResidentMinTiles) {
-    if (int rc = make_geometry(g, in, out, nullptr, 0, B, H, W, (flags & ~CURL_F_TUNE_BLOCK_MASK) | (1u << CURL_F_TUNE_UNROLL_SHIFT), 1))
-      return rc;
-    g.lds_cap = lds_for_resident(5, static_lds<chain_kernel<4, 1>>());  // with the kernel's own 8 KB of static tables: five fit
-  }
+  if (mode == 0 && !t.shape_asked && vec == 4 && tiles_of(HW / 4, B) >= kResidentMinTiles)
+    unroll = 1, lds_cap = lds_for_resident(5, static_lds<chain_kernel<4, 1>>());  // with the kernel's own 8 KB of static tables: five fit
+  return make_geometry(g, t, vec, unroll, lds_cap, HW, B);
+}
+static int launch_chain(const Geometry& g, const float* in, float* out, const float* knots, unsigned knot_stride, int n_steps,
+                        int K, const int* knot_off, const int* cin, const int* cout, int mode, hipStream_t s) {
   ChainArgs a;
   a.in = in;
   a.out = out;
@@ -452,9 +453,21 @@ static int launch_chain(const float* in, float* out, const float* knots, unsigne
   a.blocks_per_image = g.blocks_per_image;
   a.n_blocks = g.n_blocks;
   a.mode = mode;
-  hipError_t e = (g.vec == 4) ? launch_chain_u<4>(g, a, s) : launch_chain_u<1>(g, a, s);
-  if (e != hipSuccess) return hip_fail(e, "chain_kernel");
-  return 0;
+  const dim3 grid(g.blocks_per_image, g.n_images), block(g.threads);
+  dispatch_vec_mask<kMasksNone>(g.vec == 4, CURL_MASK_NONE, [&](auto V, auto) {
+    switch (g.unroll) {
+      case 1:
+        hipLaunchKernelGGL((chain_kernel<V, 1>), grid, block, g.lds_cap, s, a);
+        break;
+      case 2:
+        hipLaunchKernelGGL((chain_kernel<V, 2>), grid, block, g.lds_cap, s, a);
+        break;
+      default:
+        hipLaunchKernelGGL((chain_kernel<V, 4>), grid, block, g.lds_cap, s, a);
+        break;
+    }
+  });
+  return hip_done("chain_kernel");
 }
 
 static int chain_mode(unsigned flags) { return (flags & CURL_F_EXACT_ORDER) ? 1 : (flags & CURL_F_PWL) ? 2 : 0; }
@@ -493,32 +506,32 @@ static StripGeo strip_geo(int B, int H, int W) {
   return g;
 }
 
+// the tiles of the tri-space backward's accumulation pass (one row of partials each)
+static size_t tri_bwd_tiles(int B, int H, int W, int num_coeffs) {
+  return (num_coeffs == 126 && kTriBwdStrips) ? strip_geo(B, H, W).tiles() : tri_tiles(B, (size_t)H * W);
+}
+
 template <int V>
-static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, const float* gout, float* gcoef, float* pxbuf,
-                                      float* partial, int B, int H, int W, int residual_only, hipStream_t s) {
+static void launch_trispace_bwd(const float* img, const float* coeffs, const float* gout, float* gcoef, float* pxbuf,
+                                float* partial, int B, int H, int W, int residual_only, hipStream_t s) {
   constexpr int NC = PolyEval<V>::kCoeffs;
-  unsigned HW = (unsigned)((size_t)H * W), ppt = tri_ppt(B, HW), tiles = tri_tiles(B, HW);
-  const unsigned va = 4 * TRI_BWD_N;
-  int vec_ok = (HW % TRI_BWD_N == 0) && ((uintptr_t)img % va == 0) && ((uintptr_t)gout % va == 0) && ((uintptr_t)pxbuf % va == 0);
+  unsigned HW = (unsigned)((size_t)H * W), ppt = tri_ppt(B, HW), tiles = (unsigned)tri_bwd_tiles(B, H, W, NC);
+  // (not planes_vec4's rule: pass 1 takes TRI_BWD_N = 2 pixels per lane, as 8-byte pairs)
+  int vec_ok = (HW % TRI_BWD_N == 0) && on_grid(4 * TRI_BWD_N, img, gout, pxbuf);
   unsigned threads = (HW + TRI_BWD_N - 1) / TRI_BWD_N;
   if constexpr (V == 5) {
-    // row tiles (see make_row_geometry): block = the multiple of 64 lanes that wastes the fewest at the row end
+    // row tiles (see row_blocks): block = the multiple of 64 lanes that wastes the fewest at the row end
     int row_vec_ok = vec_ok && (W % TRI_BWD_N == 0);
-    unsigned units = ((unsigned)W + TRI_BWD_N - 1) / TRI_BWD_N, best_t = 64, best_waste = ~0u;
-    for (unsigned t = 64; t <= 256; t += 64) {
-      unsigned sg = (units + t - 1) / t, waste = sg * t - units;
-      if (waste <= best_waste) best_waste = waste, best_t = t;
-    }
-    unsigned segs = (units + best_t - 1) / best_t;
-    hipLaunchKernelGGL(trispace_bwd_px_rows_kernel, dim3(segs * (unsigned)H, (unsigned)B), dim3(best_t), 0, s, img, coeffs, gout,
-                       pxbuf, HW, (unsigned)W, (unsigned)H, units, segs, residual_only, row_vec_ok);
+    const unsigned units = ((unsigned)W + TRI_BWD_N - 1) / TRI_BWD_N;
+    const RowBlocks rb = row_blocks(units);
+    hipLaunchKernelGGL(trispace_bwd_px_rows_kernel, dim3(rb.segs * (unsigned)H, (unsigned)B), dim3(rb.threads), 0, s, img, coeffs, gout,
+                       pxbuf, HW, (unsigned)W, (unsigned)H, units, rb.segs, residual_only, row_vec_ok);
   } else {
     hipLaunchKernelGGL(trispace_bwd_px_kernel<V>, dim3((threads + 255u) / 256u, (unsigned)B), dim3(256), 0, s, img, coeffs,
                        gout, pxbuf, HW, (unsigned)W, (float)W, (float)H, residual_only, vec_ok);
   }
   if constexpr (V == 5 && kTriBwdStrips) {
     const StripGeo g = strip_geo(B, H, W);
-    tiles = g.tiles();
     CoefGradStripArgs a{pxbuf, partial, HW, (unsigned)W, (unsigned)H, g.cw_log2, g.steps, g.n_cb, g.n_rt, (unsigned)B * 3u * tiles,
                         (float)W, (float)H};
     hipLaunchKernelGGL(trispace_coef_grad_strip_kernel, dim3((a.items + 7u) / 8u * 8u * kPolyFoldXChunks), dim3(256), 0, s, a);
@@ -529,7 +542,6 @@ static hipError_t launch_trispace_bwd(const float* img, const float* coeffs, con
   }
   hipLaunchKernelGGL(trispace_coef_final_kernel, dim3((9 * NC + COEF_FINAL_OUTS - 1) / COEF_FINAL_OUTS, (unsigned)B), dim3(256),
                      0, s, partial, gcoef, tiles, 9 * NC);
-  return hipGetLastError();
 }
 
 // The stand-alone polynomial layer's coefficient gradient: a tile = 1024 * steps pixels (256 lanes x steps groups of 4),
@@ -552,76 +564,62 @@ static void launch_poly_layer_bwd(const float* img, const float* coeffs, const f
     const unsigned tiles = (unsigned)poly_bwd_tiles(B, HW);
     PolyLayerGradArgs a{img, gout, partial, (unsigned)HW, (unsigned)((HW + 3) / 4), tiles, poly_bwd_steps(B, HW), (unsigned)B * tiles};
     const dim3 grid((a.items + 7u) / 8u * 8u * PolyEval<V>::kChunks), block(256);
-    if (planes_vec4(HW, nullptr, CURL_MASK_NONE, img, gout)) hipLaunchKernelGGL((poly_layer_coef_grad_kernel<V, 4>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((poly_layer_coef_grad_kernel<V, 1>), grid, block, 0, s, a);
+    dispatch_vec_mask<kMasksNone>(planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, img, gout), CURL_MASK_NONE, [&](auto VEC, auto) {
+      hipLaunchKernelGGL((poly_layer_coef_grad_kernel<V, VEC>), grid, block, 0, s, a);
+    });
     hipLaunchKernelGGL(trispace_coef_final_kernel, dim3((3 * NC + COEF_FINAL_OUTS - 1) / COEF_FINAL_OUTS, (unsigned)B), dim3(256),
                        0, s, partial, gcoef, tiles, 3 * NC);
   }
   if (gimg) {
-    const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, img, gout, gimg);
-    const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
-    const dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
-    if (aligned) hipLaunchKernelGGL((poly_layer_img_grad_kernel<V, 4>), grid, block, 0, s, img, coeffs, gout, gimg, n);
-    else hipLaunchKernelGGL((poly_layer_img_grad_kernel<V, 1>), grid, block, 0, s, img, coeffs, gout, gimg, n);
+    const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, img, gout, gimg));
+    dispatch_vec_mask<kMasksNone>(p.aligned, CURL_MASK_NONE, [&](auto VEC, auto) {
+      hipLaunchKernelGGL((poly_layer_img_grad_kernel<V, VEC>), p.grid, dim3(256), 0, s, img, coeffs, gout, gimg, p.n);
+    });
   }
 }
 
-// What the backward entry points share once their own knot arguments are checked: the remaining argument checks, before
-// any HIP call, then the knot prep -- unless CURL_F_WS_READY: the workspace is the one the forward filled for THESE knots
-// (the autograd nodes keep it), and the prep launch and its kernel boundary go (a fifth of a training-crop-batch backward).
-static int bwd_prologue(const float* img, const float* grad_out, const void* mask, int mask_kind, unsigned flags,
-                        const void* workspace, size_t workspace_bytes, const void* scratch, size_t scratch_bytes, int B, int H,
-                        int W, int n_knots, const PrepArgs& prep, hipStream_t s, size_t scratch_need = 0,
-                        const char* scratch_msg = "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes") {
+// What the backward entry points share once their own knot arguments and the workspace are checked (knot_setup): the
+// remaining argument checks, before any HIP call, then the knot prep -- unless CURL_F_WS_READY: the workspace is the one the
+// forward filled for THESE knots (the autograd nodes keep it), and the prep launch and its kernel boundary go (a fifth of a
+// training-crop-batch backward).
+// Then what the three per-pixel backward kernels are launched with: the tile's arguments (bwd_tile.inc), one 256-thread
+// block per tile and image (p), and whether the float4 kernels apply.
+static int bwd_setup(BwdArgs& a, Pointwise& p, const float* img, const float* grad_out, float* grad_img, const void* mask,
+                     int mask_kind, unsigned flags, const KnotSetup& k, void* scratch, size_t scratch_bytes, int B, int H, int W,
+                     hipStream_t s, size_t scratch_need = 0,
+                     const char* scratch_msg = "scratch missing, misaligned or smaller than curl_layer_bwd_scratch_bytes") {
   if (int rc = check_img(img, grad_out, B, H, W)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_flags(flags, CURL_F_WS_READY)) return rc;  // (+ CURL_F_MASK_FIRST, CURL_F_TUNE_PREP: allowed everywhere)
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
   if (!scratch_need) scratch_need = curl_layer_bwd_scratch_bytes(B, H, W);
-  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < scratch_need) return fail(CURL_E_WORKSPACE, scratch_msg);
-  return (flags & CURL_F_WS_READY) ? 0 : launch_prep(prep, B, s);
-}
-
-// What the three per-pixel backward kernels are launched with, once the checks are through: the tile's arguments
-// (bwd_tile.inc), one 256-thread block per tile and image, and whether the float4 kernels apply.
-static int bwd_tile_setup(BwdArgs& a, dim3& grid, bool& aligned, const float* img, const float* grad_out, float* grad_img,
-                          const void* mask, int mask_kind, const float* ws, unsigned stride, int n_knots, void* scratch, int B,
-                          int H, int W, unsigned flags) {
+  if (int rc = check_scratch(scratch, scratch_bytes, scratch_need, true, scratch_msg)) return rc;
   const size_t HW = (size_t)H * W;
-  aligned = planes_vec4(HW, mask, mask_kind, img, grad_out, grad_img);
+  p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, img, grad_out, grad_img));
+  if (p.too_large()) return fail(CURL_E_SHAPE, "grid too large");
   a.in = img;
   a.gout = grad_out;
   a.gin = grad_img;
   a.mask = mask_kind ? mask : nullptr;
-  a.coef = ws;
+  a.coef = k.ws;
   a.partial = (float*)scratch;
-  a.coef_stride = stride;
-  a.n = (unsigned)(HW / (aligned ? 4 : 1));
-  a.blocks_per_image = (a.n + 255u) / 256u;
-  const uint64_t nb = (uint64_t)a.blocks_per_image * (uint64_t)B;
-  if (nb > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
-  a.n_blocks = (unsigned)nb;
+  a.coef_stride = k.stride;
+  a.n = p.n;
+  a.blocks_per_image = p.bpi;
+  a.n_blocks = p.bpi * (unsigned)B;
   a.mask_first = (flags & CURL_F_MASK_FIRST) ? 1 : 0;
-  a.stamp = ws_stamp((unsigned)n_knots, stride);
-  grid = dim3(a.blocks_per_image, (unsigned)B);
-  return 0;
+  a.stamp = ws_stamp((unsigned)k.n_knots, k.stride);
+  return (flags & CURL_F_WS_READY) ? 0 : launch_prep(k.prep, B, s);
 }
-// ... and the launch: KERNEL(V, M, GIN) names the instantiation; `a`, `grid` and the stream `s` are the caller's
-#define LAUNCH_BWD_TILE(V, M, KERNEL, lds)                                                 \
-  do {                                                                                     \
-    if (a.gin) hipLaunchKernelGGL((KERNEL(V, M, true)), grid, dim3(256), lds, s, a);       \
-    else hipLaunchKernelGGL((KERNEL(V, M, false)), grid, dim3(256), lds, s, a);            \
-  } while (0)
 // The second pass of the two layer forms (knots_bwd_kernel, layer_pwl_knots_bwd_kernel) takes the same arguments.
-static KnotsBwdArgs knots_bwd_args(const float* ws, const void* scratch, const float* grad_reg, float* grad_rawL, float* grad_rawR,
-                                   float* grad_rawH, int Kl, int Kr, int Kh, unsigned stride, unsigned blocks_per_image) {
+static KnotsBwdArgs knots_bwd_args(const KnotSetup& k, const void* scratch, const float* grad_reg, float* grad_rawL, float* grad_rawR,
+                                   float* grad_rawH, int Kl, int Kr, int Kh, unsigned blocks_per_image) {
   KnotsBwdArgs kb;
-  kb.ws = ws;
+  kb.ws = k.ws;
   kb.partial = (const float*)scratch;
   kb.greg = grad_reg;
   kb.graw[0] = grad_rawL, kb.graw[1] = grad_rawR, kb.graw[2] = grad_rawH;
   kb.K[0] = Kl, kb.K[1] = Kr, kb.K[2] = Kh;
-  kb.ws_stride = stride;
+  kb.ws_stride = k.stride;
   kb.blocks_per_image = blocks_per_image;
   return kb;
 }
@@ -637,42 +635,29 @@ static int stage_bwd_common(const float* img, const void* mask, int mask_kind, c
   g_err[0] = 0;
   if (!raw) return fail(CURL_E_NULL, "raw knot pointer is NULL");
   if (!grad_raw) return fail(CURL_E_NULL, "grad_raw is NULL");
-  if (int rc = check_K(K, true)) return rc;
+  KnotSetup k;
+  if (int rc = segment_knots(k, raw, NC, K, true, workspace, workspace_bytes, B, nullptr)) return rc;
   if (flags & CURL_F_PWL) return fail(CURL_E_FLAGS, "CURL_F_PWL has no backward");
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  const int n_knots = KP_TOTAL(K, NC);
-  const unsigned stride = ws_stride(n_knots);
-  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
-                            n_knots, make_prep(raw, NC, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, nullptr), s))
-    return rc;
   BwdArgs a;
-  dim3 grid;
-  bool aligned;
-  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
-    return rc;
-#define STAGE_BWD_KERNEL(V, M, G) stage_bwd_kernel<OP, V, M, G>
-  if constexpr (OP == STAGE_LAB || OP == STAGE_HSV) {
-    DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, STAGE_BWD_KERNEL, 0);
-  } else {  // no mask argument: only the CURL_MASK_NONE kernels exist
-    if (aligned) LAUNCH_BWD_TILE(4, CURL_MASK_NONE, STAGE_BWD_KERNEL, 0);
-    else LAUNCH_BWD_TILE(1, CURL_MASK_NONE, STAGE_BWD_KERNEL, 0);
-  }
-#undef STAGE_BWD_KERNEL
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, name);
+  Pointwise p;
+  if (int rc = bwd_setup(a, p, img, grad_out, grad_img, mask, mask_kind, flags, k, scratch, scratch_bytes, B, H, W, s)) return rc;
+  // (the adjust_* entries have no mask argument: only their CURL_MASK_NONE kernels exist)
+  dispatch_vec_mask<(OP == STAGE_LAB || OP == STAGE_HSV) ? kMasksAll : kMasksNone>(p.aligned, mask_kind, [&](auto V, auto M) {
+    if (a.gin) hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, true>), p.grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((stage_bwd_kernel<OP, V, M, false>), p.grid, dim3(256), 0, s, a);
+  });
+  if (int rc = hip_done(name)) return rc;
   StageKnotsArgs kb;
-  kb.ws = ws;
+  kb.ws = k.ws;
   kb.partial = (const float*)scratch;
   kb.greg = grad_reg;
   kb.graw = grad_raw;
   kb.K = K;
-  kb.ws_stride = stride;
+  kb.ws_stride = k.stride;
   kb.blocks_per_image = a.blocks_per_image;
   hipLaunchKernelGGL(stage_knots_bwd_kernel<NC>, dim3((unsigned)B), dim3(STAGE_KNOTS_THREADS), 0, s, kb);
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "stage_knots_bwd_kernel");
-  return 0;
+  return hip_done("stage_knots_bwd_kernel");
 }
 
 template <int CONV>
@@ -683,15 +668,25 @@ static int convert_bwd_common(const float* in, const float* grad_out, float* gra
   if (!grad_in) return fail(CURL_E_NULL, "grad_in is NULL");
   if (int rc = check_flags(flags, 0)) return rc;
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, in, grad_out, grad_in);
-  ConvBwdArgs a{in, grad_out, grad_in, (unsigned)(HW / (aligned ? 4 : 1))};
-  const dim3 grid((a.n + 255u) / 256u, (unsigned)B), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (aligned) hipLaunchKernelGGL((convert_bwd_kernel<CONV, 4>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((convert_bwd_kernel<CONV, 1>), grid, block, 0, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, name);
-  return 0;
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, in, grad_out, grad_in));
+  ConvBwdArgs a{in, grad_out, grad_in, p.n};
+  dispatch_vec_mask<kMasksNone>(p.aligned, CURL_MASK_NONE, [&](auto V, auto) {
+    hipLaunchKernelGGL((convert_bwd_kernel<CONV, V>), p.grid, dim3(256), 0, (hipStream_t)stream, a);
+  });
+  return hip_done(name);
+}
+
+// the byte egress, with the white background where `mask` is given: float planes in (16-byte grid), interleaved bytes out (4)
+template <MaskKinds MASKS>
+static int launch_egress(const float* in, const void* mask, int mask_kind, uint8_t* out, int B, int H, int W, curl_stream_t stream,
+                         const char* name) {
+  const size_t HW = (size_t)H * W;
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, in) && on_grid(4, out));
+  dispatch_vec_mask<MASKS>(p.aligned, mask_kind, [&](auto V, auto M) {
+    hipLaunchKernelGGL((f32chw_to_u8hwc_kernel<V, M>), p.grid, dim3(256), aux_lds(kResEgress, p.grid, V == 4, static_lds<f32chw_to_u8hwc_kernel<V, M>>()),
+                       (hipStream_t)stream, in, mask, out, p.n);
+  });
+  return hip_done(name);
 }
 
 extern "C" {
@@ -721,13 +716,14 @@ int curl_apply_curve_f32(const float* img, const float* C, float* out, float* re
     return fail(CURL_E_SHAPE, "channel_in/channel_out must be 0, 1 or 2");
   if (int rc = check_flags(flags, CURL_F_EXACT_ORDER | CURL_F_PWL)) return rc;
   hipStream_t s = (hipStream_t)stream;
+  Geometry g;
+  if (int rc = plan_chain(g, img, out, chain_mode(flags), B, H, W, flags)) return rc;
   if (reg) {
     hipLaunchKernelGGL(curve_reg_kernel, dim3((B + 63) / 64), dim3(64), 0, s, C, reg, B, K);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "curve_reg_kernel");
+    if (int rc = hip_done("curve_reg_kernel")) return rc;
   }
   int off[1] = {0}, ci[1] = {channel_in}, co[1] = {channel_out};
-  return launch_chain(img, out, C, (unsigned)K, 1, K, off, ci, co, chain_mode(flags), B, H, W, flags, s);
+  return launch_chain(g, img, out, C, (unsigned)K, 1, K, off, ci, co, chain_mode(flags), s);
 }
 
 static int adjust_common(const float* img, const float* raw, float* out, float* reg, void* workspace,
@@ -737,20 +733,18 @@ static int adjust_common(const float* img, const float* raw, float* out, float* 
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!raw) return fail(CURL_E_NULL, "raw knot pointer is NULL");
   if (int rc = check_flags(flags, CURL_F_EXACT_ORDER | CURL_F_PWL)) return rc;
-  if (int rc = check_K(K, chain_mode(flags) == 0)) return rc;
-  if (int rc = check_ws(workspace, workspace_bytes, B, KP_TOTAL(K, n_curves))) return rc;
+  KnotSetup k;
+  if (int rc = segment_knots(k, raw, n_curves, K, chain_mode(flags) == 0, workspace, workspace_bytes, B, reg)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned stride = ws_stride(KP_TOTAL(K, n_curves));
-  const PrepArgs prep = make_prep(raw, n_curves, K, nullptr, 0, 0, nullptr, 0, 0, ws, stride, reg);
   int mode = chain_mode(flags);
   if (mode == 0) {
     if (n_curves == 3)
-      return launch_stream<OpAdjust3>(img, out, nullptr, 0, ws, stride, B, H, W, flags, s, "adjust3", 0, Slab(), &prep);
-    return launch_stream<OpAdjustHsv>(img, out, nullptr, 0, ws, stride, B, H, W, flags, s, "adjust_hsv", 0, Slab(), &prep);
+      return launch_stream<OpAdjust3>(img, out, nullptr, 0, k.ws, k.stride, B, H, W, flags, s, "adjust3", 0, Slab(), &k.prep);
+    return launch_stream<OpAdjustHsv>(img, out, nullptr, 0, k.ws, k.stride, B, H, W, flags, s, "adjust_hsv", 0, Slab(), &k.prep);
   }
-  if (int rc = launch_prep(prep, B, s)) return rc;
-  flags &= ~CURL_F_TUNE_PREP_MASK;
+  Geometry g;
+  if (int rc = plan_chain(g, img, out, mode, B, H, W, flags)) return rc;
+  if (int rc = launch_prep(k.prep, B, s)) return rc;
   int off[4], ci[4], co[4];
   for (int c = 0; c < n_curves; ++c) off[c] = WS_KNOTS + c * K;
   if (n_curves == 3) {
@@ -761,7 +755,7 @@ static int adjust_common(const float* img, const float* raw, float* out, float* 
     ci[2] = 1, co[2] = 1;  // curves.py:73-74
     ci[3] = 2, co[3] = 2;  // curves.py:79-80
   }
-  return launch_chain(img, out, ws, stride, n_curves, K, off, ci, co, mode, B, H, W, flags, s);
+  return launch_chain(g, img, out, k.ws, k.stride, n_curves, K, off, ci, co, mode, s);
 }
 
 int curl_adjust_rgb_f32(const float* img, const float* raw, float* out, float* reg, void* workspace,
@@ -797,20 +791,17 @@ int curl_lab_stage_f32(const float* img, const void* mask, int mask_kind, const 
   if (!rawL) return fail(CURL_E_NULL, "rawL is NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_flags(flags, CURL_F_PWL | CURL_F_EXACT_ORDER)) return rc;
-  if (int rc = check_K(Kl, chain_mode(flags) == 0)) return rc;
-  if (int rc = check_ws(workspace, workspace_bytes, B, KP_TOTAL(Kl, 3))) return rc;
+  KnotSetup k;
+  if (int rc = segment_knots(k, rawL, 3, Kl, chain_mode(flags) == 0, workspace, workspace_bytes, B, reg)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned stride = ws_stride(KP_TOTAL(Kl, 3));
-  const PrepArgs prep = make_prep(rawL, 3, Kl, nullptr, 0, 0, nullptr, 0, 0, ws, stride, reg);
   if (flags & CURL_F_PWL)  // the paper's clamped piecewise-linear curves, knots in LDS
-    return launch_stream<OpLabStageTab<0>>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W,
-                                           flags & ~CURL_F_PWL, s, "lab_stage_pwl", Kl, Slab(), &prep);
+    return launch_stream<OpLabStageTab<0>>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W,
+                                           flags & ~CURL_F_PWL, s, "lab_stage_pwl", Kl, Slab(), &k.prep);
   if (flags & CURL_F_EXACT_ORDER)  // validation mode: every curve as the reference's term-by-term float32 sum
-    return launch_stream<OpLabStageTab<1>>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W,
-                                           flags & ~CURL_F_EXACT_ORDER, s, "lab_stage_exact", Kl, Slab(), &prep);
-  return launch_stream<OpLabStage>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W, flags, s,
-                                   "lab_stage", 0, Slab(), &prep);
+    return launch_stream<OpLabStageTab<1>>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W,
+                                           flags & ~CURL_F_EXACT_ORDER, s, "lab_stage_exact", Kl, Slab(), &k.prep);
+  return launch_stream<OpLabStage>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W, flags, s,
+                                   "lab_stage", 0, Slab(), &k.prep);
 }
 
 int curl_hsv_stage_f32(const float* img, const void* mask, int mask_kind, const float* rawH, float* out, float* reg,
@@ -820,19 +811,19 @@ int curl_hsv_stage_f32(const float* img, const void* mask, int mask_kind, const 
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!rawH) return fail(CURL_E_NULL, "rawH is NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
-  if (int rc = check_K(Kh, true)) return rc;
   if (int rc = check_flags(flags, 0)) return rc;
-  if (int rc = check_ws(workspace, workspace_bytes, B, KP_TOTAL(Kh, 4))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned stride = ws_stride(KP_TOTAL(Kh, 4));
-  const PrepArgs prep = make_prep(rawH, 4, Kh, nullptr, 0, 0, nullptr, 0, 0, ws, stride, reg);
-  return launch_stream<OpHsvStage>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W, flags, s,
-                                   "hsv_stage", 0, Slab(), &prep);
+  KnotSetup k;
+  if (int rc = segment_knots(k, rawH, 4, Kh, true, workspace, workspace_bytes, B, reg)) return rc;
+  return launch_stream<OpHsvStage>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W, flags,
+                                   (hipStream_t)stream, "hsv_stage", 0, Slab(), &k.prep);
 }
 
-static int check_slab(int H, int row0, int rows) {
+// the two *_slab_* entries: rows [row0, row0 + rows) of images H rows high, checked before the rows stand in for H
+static int slab_of(Slab& slab, int H, int W, int row0, int rows) {
+  if (H <= 0) return fail(CURL_E_SHAPE, "B, H, W must be positive");
   if (row0 < 0 || rows <= 0 || (int64_t)row0 + rows > H) return fail(CURL_E_SHAPE, "row slab [row0, row0 + rows) must lie inside [0, H)");
+  if ((uint64_t)H * (uint64_t)(W > 0 ? W : 0) > (1ull << 30)) return fail(CURL_E_SHAPE, "H*W exceeds 2^30 pixels");
+  slab.H_full = H, slab.row0 = row0;
   return 0;
 }
 
@@ -843,22 +834,18 @@ static int layer_fwd_impl(const float* img, const void* mask, int mask_kind, con
   if (int rc = check_mask(mask, mask_kind)) return rc;
   // (CURL_F_DIAG_SKIP_PREP: accepted by these two entries only -- it makes the kernel read a workspace the caller vouches for)
   if (int rc = check_flags(flags, CURL_F_PWL | CURL_F_EXACT_ORDER | CURL_F_DIAG_SKIP_PREP)) return rc;
-  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, chain_mode(flags) == 0)) return rc;
-  int n_knots = layer_n_knots(Kl, Kr, Kh);
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, chain_mode(flags) == 0, workspace, workspace_bytes, B, reg)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned stride = ws_stride(n_knots);
-  const PrepArgs prep_args = make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, reg);
-  const PrepArgs* prep = (flags & CURL_F_DIAG_SKIP_PREP) ? nullptr : &prep_args;
+  const PrepArgs* prep = (flags & CURL_F_DIAG_SKIP_PREP) ? nullptr : &k.prep;
   flags &= ~CURL_F_DIAG_SKIP_PREP;
   if (flags & CURL_F_PWL)  // the paper's clamped piecewise-linear curves, all ten of them from LDS
-    return launch_stream<OpLayerTab<0>>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W,
+    return launch_stream<OpLayerTab<0>>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W,
                                         flags & ~CURL_F_PWL, s, "curl_layer_pwl", Kl | (Kr << 10) | (Kh << 20), slab, prep);
   if (flags & CURL_F_EXACT_ORDER)  // validation mode (SURVEY.md 7.2): curves.py:31-32 term by term, reference stage order
-    return launch_stream<OpLayerTab<1>>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W,
+    return launch_stream<OpLayerTab<1>>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W,
                                         flags & ~CURL_F_EXACT_ORDER, s, "curl_layer_exact", Kl | (Kr << 10) | (Kh << 20), slab, prep);
-  return launch_stream<OpLayer>(img, out, mask_kind ? mask : nullptr, mask_kind, ws, stride, B, H, W, flags, s,
+  return launch_stream<OpLayer>(img, out, mask_kind ? mask : nullptr, mask_kind, k.ws, k.stride, B, H, W, flags, s,
                                 "curl_layer", 0, slab, prep);
 }
 
@@ -874,11 +861,8 @@ int curl_layer_fwd_slab_f32(const float* img, const void* mask, int mask_kind, c
                             const float* rawH, float* out, float* reg, void* workspace, size_t workspace_bytes, int B, int H,
                             int W, int row0, int rows, int Kl, int Kr, int Kh, unsigned flags, curl_stream_t stream) {
   g_err[0] = 0;
-  if (H <= 0) return fail(CURL_E_SHAPE, "B, H, W must be positive");
-  if (int rc = check_slab(H, row0, rows)) return rc;
-  if ((uint64_t)H * (uint64_t)(W > 0 ? W : 0) > (1ull << 30)) return fail(CURL_E_SHAPE, "H*W exceeds 2^30 pixels");
   Slab slab;
-  slab.H_full = H, slab.row0 = row0;
+  if (int rc = slab_of(slab, H, W, row0, rows)) return rc;
   return layer_fwd_impl(img, mask, mask_kind, rawL, rawR, rawH, out, reg, workspace, workspace_bytes, B, rows, W, Kl, Kr,
                         Kh, flags, stream, slab);
 }
@@ -889,17 +873,12 @@ int curl_layer_fwd_u8hwc(const uint8_t* img, const void* mask, int mask_kind, co
                          curl_stream_t stream) {
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
-  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point");
-  int n_knots = layer_n_knots(Kl, Kr, Kh);
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  unsigned stride = ws_stride(n_knots);
-  if (int rc = run_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, reg, B, s)) return rc;
-  return launch_stream_u8<OpLayer>(img, out, mask_kind ? mask : nullptr, mask_kind, white_mask, ws, stride, B, H, W, s,
-                                   "curl_layer_u8hwc");
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, true, workspace, workspace_bytes, B, reg)) return rc;
+  return launch_stream_u8<OpLayer>(img, out, mask_kind ? mask : nullptr, mask_kind, white_mask, k.ws, k.stride, B, H, W,
+                                   (hipStream_t)stream, "curl_layer_u8hwc", &k.prep);
 }
 
 size_t curl_layer_bwd_scratch_bytes(int B, int H, int W) {
@@ -915,30 +894,21 @@ int curl_layer_bwd_f32(const float* img, const void* mask, int mask_kind, const 
                        void* scratch, size_t scratch_bytes, int B, int H, int W, int Kl, int Kr, int Kh, unsigned flags,
                        curl_stream_t stream) {
   g_err[0] = 0;
-  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, true, workspace, workspace_bytes, B, nullptr)) return rc;
   if (!grad_rawL || !grad_rawR || !grad_rawH) return fail(CURL_E_NULL, "grad_rawL/R/H must all be non-NULL");
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  const int n_knots = layer_n_knots(Kl, Kr, Kh);
-  const unsigned stride = ws_stride(n_knots);
-  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
-                            n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s))
-    return rc;
   BwdArgs a;
-  dim3 grid;
-  bool aligned;
-  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
-    return rc;
-#define LAYER_BWD_KERNEL(V, M, G) layer_bwd_kernel<V, M, G>
-  DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, LAYER_BWD_KERNEL, 0);
-#undef LAYER_BWD_KERNEL
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "layer_bwd_kernel");
-  const KnotsBwdArgs kb = knots_bwd_args(ws, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, stride, a.blocks_per_image);
+  Pointwise p;
+  if (int rc = bwd_setup(a, p, img, grad_out, grad_img, mask, mask_kind, flags, k, scratch, scratch_bytes, B, H, W, s)) return rc;
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    if (a.gin) hipLaunchKernelGGL((layer_bwd_kernel<V, M, true>), p.grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((layer_bwd_kernel<V, M, false>), p.grid, dim3(256), 0, s, a);
+  });
+  if (int rc = hip_done("layer_bwd_kernel")) return rc;
+  const KnotsBwdArgs kb = knots_bwd_args(k, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, a.blocks_per_image);
   hipLaunchKernelGGL(knots_bwd_kernel, dim3(B), dim3(KNOTS_BWD_THREADS), 0, s, kb);
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "knots_bwd_kernel");
-  return 0;
+  return hip_done("knots_bwd_kernel");
 }
 
 size_t curl_layer_pwl_bwd_scratch_bytes(int B, int H, int W, int Kl, int Kr, int Kh) {
@@ -957,34 +927,27 @@ int curl_layer_pwl_bwd_f32(const float* img, const void* mask, int mask_kind, co
                            void* scratch, size_t scratch_bytes, int B, int H, int W, int Kl, int Kr, int Kh, unsigned flags,
                            curl_stream_t stream) {
   g_err[0] = 0;
-  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, false)) return rc;
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, false, workspace, workspace_bytes, B, nullptr)) return rc;
   if (!grad_rawL || !grad_rawR || !grad_rawH) return fail(CURL_E_NULL, "grad_rawL/R/H must all be non-NULL");
   if (flags & ~(CURL_F_WS_READY | CURL_F_MASK_FIRST)) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point");
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  const int n_knots = layer_n_knots(Kl, Kr, Kh);
-  const unsigned stride = ws_stride(n_knots);
   const size_t need = (B > 0 && H > 0 && W > 0) ? curl_layer_pwl_bwd_scratch_bytes(B, H, W, Kl, Kr, Kh) : 0;
-  if (int rc = bwd_prologue(img, grad_out, mask, mask_kind, flags, workspace, workspace_bytes, scratch, scratch_bytes, B, H, W,
-                            n_knots, make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, nullptr), s, need,
-                            "scratch missing, misaligned or smaller than curl_layer_pwl_bwd_scratch_bytes"))
-    return rc;
   PwlBwdArgs a;
-  dim3 grid;
-  bool aligned;
-  if (int rc = bwd_tile_setup(a, grid, aligned, img, grad_out, grad_img, mask, mask_kind, ws, stride, n_knots, scratch, B, H, W, flags))
+  Pointwise p;
+  if (int rc = bwd_setup(a, p, img, grad_out, grad_img, mask, mask_kind, flags, k, scratch, scratch_bytes, B, H, W, s, need,
+                         "scratch missing, misaligned or smaller than curl_layer_pwl_bwd_scratch_bytes"))
     return rc;
   a.kl = Kl, a.kr = Kr, a.kh = Kh;
-#define PWL_BWD_KERNEL(V, M, G) layer_pwl_bwd_kernel<V, M, G>
-  DISPATCH_VEC_MASK(LAUNCH_BWD_TILE, aligned, mask_kind, PWL_BWD_KERNEL, pwl_bwd_lds_bytes(Kl, Kr, Kh));
-#undef PWL_BWD_KERNEL
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "layer_pwl_bwd_kernel");
-  const KnotsBwdArgs kb = knots_bwd_args(ws, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, stride, a.blocks_per_image);
+  const size_t lds = pwl_bwd_lds_bytes(Kl, Kr, Kh);
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    if (a.gin) hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, true>), p.grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((layer_pwl_bwd_kernel<V, M, false>), p.grid, dim3(256), lds, s, a);
+  });
+  if (int rc = hip_done("layer_pwl_bwd_kernel")) return rc;
+  const KnotsBwdArgs kb = knots_bwd_args(k, scratch, grad_reg, grad_rawL, grad_rawR, grad_rawH, Kl, Kr, Kh, a.blocks_per_image);
   hipLaunchKernelGGL(layer_pwl_knots_bwd_kernel, dim3(MAX_CURVES, (unsigned)B), dim3(PWL_KNOTS_THREADS), 0, s, kb);
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "layer_pwl_knots_bwd_kernel");
-  return 0;
+  return hip_done("layer_pwl_knots_bwd_kernel");
 }
 
 int curl_adjust_rgb_bwd_f32(const float* img, const float* raw, const float* grad_out, const float* grad_reg,
@@ -1043,8 +1006,7 @@ static int trispace_fwd_impl(const float* img, const float* coeffs, float* out, 
                              unsigned flags, curl_stream_t stream, Slab slab) {
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (num_coeffs != 126 && num_coeffs != 35)
-    return fail(CURL_E_KNOTS, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)");
+  if (int rc = check_num_coeffs(num_coeffs, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)")) return rc;
   if (int rc = check_flags(flags, CURL_F_RESIDUAL_ONLY)) return rc;
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
   int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
@@ -1064,11 +1026,8 @@ int curl_trispace_fwd_f32(const float* img, const float* coeffs, float* out, int
 int curl_trispace_fwd_slab_f32(const float* img, const float* coeffs, float* out, int B, int H, int W, int row0, int rows,
                                int num_coeffs, unsigned flags, curl_stream_t stream) {
   g_err[0] = 0;
-  if (H <= 0) return fail(CURL_E_SHAPE, "B, H, W must be positive");
-  if (int rc = check_slab(H, row0, rows)) return rc;
-  if ((uint64_t)H * (uint64_t)(W > 0 ? W : 0) > (1ull << 30)) return fail(CURL_E_SHAPE, "H*W exceeds 2^30 pixels");
   Slab slab;
-  slab.H_full = H, slab.row0 = row0;
+  if (int rc = slab_of(slab, H, W, row0, rows)) return rc;
   return trispace_fwd_impl(img, coeffs, out, B, rows, W, num_coeffs, flags, stream, slab);
 }
 
@@ -1077,8 +1036,7 @@ int curl_trispace_fwd_u8hwc(const uint8_t* img, const float* coeffs, const uint8
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (num_coeffs != 126 && num_coeffs != 35)
-    return fail(CURL_E_KNOTS, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)");
+  if (int rc = check_num_coeffs(num_coeffs, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)")) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (the byte output is an image)");
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -1093,24 +1051,14 @@ int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (num_variables != 5 && num_variables != 3) return fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)");
+  if (int rc = check_num_variables(num_variables)) return rc;
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, img, out);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
-  dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_POLY(V, VEC) hipLaunchKernelGGL((poly_layer_kernel<V, VEC>), grid, block, 0, s, img, coeffs, out, n)
-  if (num_variables == 5) {
-    if (aligned) LAUNCH_POLY(5, 4);
-    else LAUNCH_POLY(5, 1);
-  } else {
-    if (aligned) LAUNCH_POLY(3, 4);
-    else LAUNCH_POLY(3, 1);
-  }
-#undef LAUNCH_POLY
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "poly_layer_kernel");
-  return 0;
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, img, out));
+  dispatch_vec_mask<kMasksNone>(p.aligned, CURL_MASK_NONE, [&](auto VEC, auto) {
+    if (num_variables == 5) hipLaunchKernelGGL((poly_layer_kernel<5, VEC>), p.grid, dim3(256), 0, (hipStream_t)stream, img, coeffs, out, p.n);
+    else hipLaunchKernelGGL((poly_layer_kernel<3, VEC>), p.grid, dim3(256), 0, (hipStream_t)stream, img, coeffs, out, p.n);
+  });
+  return hip_done("poly_layer_kernel");
 }
 
 int curl_u8hwc_to_f32chw(const uint8_t* in, float* out, int B, int H, int W, int Cin, curl_stream_t stream) {
@@ -1118,28 +1066,17 @@ int curl_u8hwc_to_f32chw(const uint8_t* in, float* out, int B, int H, int W, int
   if (int rc = check_img(in, out, B, H, W)) return rc;
   if (Cin != 3 && Cin != 4) return fail(CURL_E_SHAPE, "Cin must be 3 (RGB) or 4 (RGBA)");
   const size_t HW = (size_t)H * W;
-  const bool aligned = (HW % 4 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)in % (Cin == 4 ? 16 : 4) == 0);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
-  dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
-  if (aligned) hipLaunchKernelGGL(u8hwc_to_f32chw_kernel<4>, grid, block, aux_lds(kResIngress, grid, true, static_lds<u8hwc_to_f32chw_kernel<4>>()), (hipStream_t)stream, in, out, n, Cin);
-  else hipLaunchKernelGGL(u8hwc_to_f32chw_kernel<1>, grid, block, 0, (hipStream_t)stream, in, out, n, Cin);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "u8hwc_to_f32chw");
-  return 0;
+  // (four RGBA pixels are one 16-byte load, four RGB pixels three dwords)
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, out) && on_grid(Cin == 4 ? 16 : 4, in));
+  if (p.aligned) hipLaunchKernelGGL(u8hwc_to_f32chw_kernel<4>, p.grid, dim3(256), aux_lds(kResIngress, p.grid, true, static_lds<u8hwc_to_f32chw_kernel<4>>()), (hipStream_t)stream, in, out, p.n, Cin);
+  else hipLaunchKernelGGL(u8hwc_to_f32chw_kernel<1>, p.grid, dim3(256), 0, (hipStream_t)stream, in, out, p.n, Cin);
+  return hip_done("u8hwc_to_f32chw");
 }
 
 int curl_f32chw_to_u8hwc(const float* in, uint8_t* out, int B, int H, int W, curl_stream_t stream) {
   g_err[0] = 0;
   if (int rc = check_img(in, out, B, H, W)) return rc;
-  const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, nullptr, CURL_MASK_NONE, in) && ((uintptr_t)out % 4 == 0);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
-  dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
-  if (aligned) hipLaunchKernelGGL((f32chw_to_u8hwc_kernel<4, CURL_MASK_NONE>), grid, block, aux_lds(kResEgress, grid, true, static_lds<f32chw_to_u8hwc_kernel<4, CURL_MASK_NONE>>()), (hipStream_t)stream, in, nullptr, out, n);
-  else hipLaunchKernelGGL((f32chw_to_u8hwc_kernel<1, CURL_MASK_NONE>), grid, block, 0, (hipStream_t)stream, in, nullptr, out, n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "f32chw_to_u8hwc");
-  return 0;
+  return launch_egress<kMasksNone>(in, nullptr, CURL_MASK_NONE, out, B, H, W, stream, "f32chw_to_u8hwc");
 }
 
 int curl_compose_white_u8hwc(const float* in, const void* mask, int mask_kind, uint8_t* out, int B, int H, int W,
@@ -1148,23 +1085,7 @@ int curl_compose_white_u8hwc(const float* in, const void* mask, int mask_kind, u
   if (int rc = check_img(in, out, B, H, W)) return rc;
   if (mask_kind != CURL_MASK_U8 && mask_kind != CURL_MASK_F32) return fail(CURL_E_MASK, "mask_kind must be 1 (u8) or 2 (f32)");
   if (!mask) return fail(CURL_E_MASK, "mask is NULL");
-  const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, in) && ((uintptr_t)out % 4 == 0);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1));
-  dim3 grid((n + 255u) / 256u, (unsigned)B), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_EGRESS(V, M) hipLaunchKernelGGL((f32chw_to_u8hwc_kernel<V, M>), grid, block, aux_lds(kResEgress, grid, V == 4, static_lds<f32chw_to_u8hwc_kernel<V, M>>()), s, in, mask, out, n)
-  if (aligned) {
-    if (mask_kind == CURL_MASK_U8) LAUNCH_EGRESS(4, CURL_MASK_U8);
-    else LAUNCH_EGRESS(4, CURL_MASK_F32);
-  } else {
-    if (mask_kind == CURL_MASK_U8) LAUNCH_EGRESS(1, CURL_MASK_U8);
-    else LAUNCH_EGRESS(1, CURL_MASK_F32);
-  }
-#undef LAUNCH_EGRESS
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "compose_white_u8hwc");
-  return 0;
+  return launch_egress<kMasksU8F32>(in, mask, mask_kind, out, B, H, W, stream, "compose_white_u8hwc");
 }
 
 size_t curl_psnr_scratch_bytes(int B, int H, int W) {
@@ -1179,21 +1100,18 @@ int curl_psnr_f32(const float* a, const float* b, const void* mask, int mask_kin
   if (int rc = check_img(a, b, B, H, W)) return rc;
   if (!psnr) return fail(CURL_E_NULL, "psnr output is NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
-  if (!scratch || scratch_bytes < curl_psnr_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing or smaller than curl_psnr_scratch_bytes");
+  if (int rc = check_scratch(scratch, scratch_bytes, curl_psnr_scratch_bytes(B, H, W), false, "scratch missing or smaller than curl_psnr_scratch_bytes"))
+    return rc;
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, a, b);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1)), bpi = (n + 255u) / 256u;  // <= the blocks the scratch is sized for
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, a, b));  // p.bpi <= the blocks the scratch is sized for
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(bpi, (unsigned)B), block(256);
-#define LAUNCH_PSNR(V, M) hipLaunchKernelGGL((psnr_partial_kernel<V, M>), grid, block, aux_lds(kResPsnr, grid, V == 4, static_lds<psnr_partial_kernel<V, M>>()), s, a, b, mask, (float*)scratch, n, bpi)
-  DISPATCH_VEC_MASK(LAUNCH_PSNR, aligned, mask_kind);
-#undef LAUNCH_PSNR
-  hipLaunchKernelGGL(psnr_final_kernel, dim3((unsigned)B), dim3(256), 0, s, (const float*)scratch, psnr, bpi,
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    hipLaunchKernelGGL((psnr_partial_kernel<V, M>), p.grid, dim3(256), aux_lds(kResPsnr, p.grid, V == 4, static_lds<psnr_partial_kernel<V, M>>()), s,
+                       a, b, mask, (float*)scratch, p.n, p.bpi);
+  });
+  hipLaunchKernelGGL(psnr_final_kernel, dim3((unsigned)B), dim3(256), 0, s, (const float*)scratch, psnr, p.bpi,
                      max_intensity);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "psnr kernels");
-  return 0;
+  return hip_done("psnr kernels");
 }
 
 #define MSSSIM_LEVELS 5
@@ -1227,9 +1145,8 @@ static int ssim_check(const void* a, const void* b, int B, int C, int H, int W, 
     return fail(CURL_E_SHAPE, "MS-SSIM needs H, W >= 32 (five pyramid levels, each followed by a 2x2 pooling)");
   if ((uint64_t)H * (uint64_t)W > (1ull << 30) || (uint64_t)B * C > 65535) return fail(CURL_E_SHAPE, "image too large");
   if (ws < 1 || ws > 2 * SSIM_R + 1 || (ws & 1) == 0) return fail(CURL_E_KNOTS, "window_size must be odd and <= 11");
-  if (!scratch || (uintptr_t)scratch % 16 || bytes < curl_msssim_scratch_bytes(B, C, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_msssim_scratch_bytes");
-  return 0;
+  return check_scratch(scratch, bytes, curl_msssim_scratch_bytes(B, C, H, W), true,
+                       "scratch missing, misaligned or smaller than curl_msssim_scratch_bytes");
 }
 static void ssim_window(int ws, float* g) {  // metric.py:104-118: exp(-(x - ws//2)^2 / (2 sigma^2)), sigma 1.5, normalised
   float sum = 0.0f;
@@ -1240,8 +1157,8 @@ static void ssim_window(int ws, float* g) {  // metric.py:104-118: exp(-(x - ws/
   for (int x = 0; x < ws; ++x) g[x] /= sum;
 }
 // runs the forward level kernels: pyramids of a and b into scratch, per-level means into ssims/mcs when asked
-static hipError_t ssim_forward_levels(const float* a, const float* b, float* ssims, float* mcs, float* scr, const SsimPlan& pl,
-                                      int B, int C, int H, int W, int ws, int last_level, hipStream_t s) {
+static void ssim_forward_levels(const float* a, const float* b, float* ssims, float* mcs, float* scr, const SsimPlan& pl,
+                                int B, int C, int H, int W, int ws, int last_level, hipStream_t s) {
   float* pyr_a = scr;
   float* pyr_b = scr + pl.pyr;
   float* partial = scr + 3 * pl.pyr + 3 * pl.maps;
@@ -1263,7 +1180,6 @@ static hipError_t ssim_forward_levels(const float* a, const float* b, float* ssi
                          (unsigned)C * k.tiles, 1.0 / ((double)C * h * w), l, MSSSIM_LEVELS);
     la = k.a_next, lb = k.b_next;
   }
-  return hipGetLastError();
 }
 
 int curl_msssim_fwd_f32(const float* a, const float* b, float* ssims, float* mcs, void* scratch, size_t scratch_bytes,
@@ -1272,10 +1188,8 @@ int curl_msssim_fwd_f32(const float* a, const float* b, float* ssims, float* mcs
   if (int rc = ssim_check(a, b, B, C, H, W, window_size, scratch, scratch_bytes)) return rc;
   if (!ssims || !mcs) return fail(CURL_E_NULL, "ssims / mcs output is NULL");
   SsimPlan pl = ssim_plan(B, C, H, W);
-  hipError_t e = ssim_forward_levels(a, b, ssims, mcs, (float*)scratch, pl, B, C, H, W, window_size, MSSSIM_LEVELS - 1,
-                                     (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "msssim forward kernels");
-  return 0;
+  ssim_forward_levels(a, b, ssims, mcs, (float*)scratch, pl, B, C, H, W, window_size, MSSSIM_LEVELS - 1, (hipStream_t)stream);
+  return hip_done("msssim forward kernels");
 }
 
 int curl_msssim_bwd_f32(const float* a, const float* b, const float* g_ssims, const float* g_mcs, float* grad_a,
@@ -1288,8 +1202,8 @@ int curl_msssim_bwd_f32(const float* a, const float* b, const float* g_ssims, co
   hipStream_t s = (hipStream_t)stream;
   float* scr = (float*)scratch;
   // the pyramids again (stateless between the two calls): levels 1..4 of a and b
-  hipError_t e = ssim_forward_levels(a, b, nullptr, nullptr, scr, pl, B, C, H, W, window_size, MSSSIM_LEVELS - 2, s);
-  if (e != hipSuccess) return hip_fail(e, "msssim pyramid kernels");
+  ssim_forward_levels(a, b, nullptr, nullptr, scr, pl, B, C, H, W, window_size, MSSSIM_LEVELS - 2, s);
+  if (int rc = hip_done("msssim pyramid kernels")) return rc;
   float* pyr_a = scr;
   float* pyr_b = scr + pl.pyr;
   float* pyr_g = scr + 2 * pl.pyr;
@@ -1314,9 +1228,7 @@ int curl_msssim_bwd_f32(const float* a, const float* b, const float* g_ssims, co
     ssim_window(window_size, q.g);
     hipLaunchKernelGGL(msssim_grad_kernel, dim3(k.tiles, (unsigned)(B * C)), dim3(256), 0, s, q);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "msssim backward kernels");
-  return 0;
+  return hip_done("msssim backward kernels");
 }
 
 size_t curl_loss_terms_scratch_bytes(int B, int H, int W) {
@@ -1331,21 +1243,18 @@ int curl_loss_terms_f32(const float* pred, const float* target, const void* mask
   if (int rc = check_img(pred, target, B, H, W)) return rc;
   if (!sums) return fail(CURL_E_NULL, "sums is NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
-  if (!scratch || scratch_bytes < curl_loss_terms_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing or smaller than curl_loss_terms_scratch_bytes");
+  if (int rc = check_scratch(scratch, scratch_bytes, curl_loss_terms_scratch_bytes(B, H, W), false,
+                             "scratch missing or smaller than curl_loss_terms_scratch_bytes"))
+    return rc;
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, pred, target, L_pred, L_target);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1)), bpi = (n + 255u) / 256u;  // <= the blocks the scratch is sized for
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, pred, target, L_pred, L_target));  // p.bpi <= the blocks the scratch is sized for
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(bpi, (unsigned)B), block(256);
-#define LAUNCH_LOSS(V, M) \
-  hipLaunchKernelGGL((loss_terms_kernel<V, M>), grid, block, aux_lds(kResLoss, grid, V == 4, 0), s, pred, target, mask, (float*)scratch, L_pred, L_target, n, bpi)
-  DISPATCH_VEC_MASK(LAUNCH_LOSS, aligned, mask_kind);
-#undef LAUNCH_LOSS
-  hipLaunchKernelGGL(loss_terms_final_kernel, dim3((unsigned)B), dim3(LOSS_FINAL_THREADS), 0, s, (const float*)scratch, sums, bpi);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "loss_terms kernels");
-  return 0;
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    hipLaunchKernelGGL((loss_terms_kernel<V, M>), p.grid, dim3(256), aux_lds(kResLoss, p.grid, V == 4, 0), s, pred, target, mask, (float*)scratch,
+                       L_pred, L_target, p.n, p.bpi);
+  });
+  hipLaunchKernelGGL(loss_terms_final_kernel, dim3((unsigned)B), dim3(LOSS_FINAL_THREADS), 0, s, (const float*)scratch, sums, p.bpi);
+  return hip_done("loss_terms kernels");
 }
 
 int curl_layer_loss_fwd_f32(const float* img, const void* mask, int mask_kind, const float* rawL, const float* rawR,
@@ -1355,41 +1264,31 @@ int curl_layer_loss_fwd_f32(const float* img, const void* mask, int mask_kind, c
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!target || !sums) return fail(CURL_E_NULL, "target / sums is NULL");
-  if (int rc = check_layer_knots(rawL, rawR, rawH, Kl, Kr, Kh, true)) return rc;
   if (int rc = check_mask(mask, mask_kind)) return rc;
   if (int rc = check_flags(flags, 0)) return rc;
-  const int n_knots = layer_n_knots(Kl, Kr, Kh);
-  if (int rc = check_ws(workspace, workspace_bytes, B, n_knots)) return rc;
-  if (!scratch || scratch_bytes < curl_loss_terms_scratch_bytes(B, H, W))
-    return fail(CURL_E_WORKSPACE, "scratch missing or smaller than curl_loss_terms_scratch_bytes");
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, true, workspace, workspace_bytes, B, reg)) return rc;
+  if (int rc = check_scratch(scratch, scratch_bytes, curl_loss_terms_scratch_bytes(B, H, W), false,
+                             "scratch missing or smaller than curl_loss_terms_scratch_bytes"))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* ws = (float*)workspace;
-  const unsigned stride = ws_stride(n_knots);
-  const PrepArgs prep = make_prep(rawL, 3, Kl, rawR, 3, Kr, rawH, 4, Kh, ws, stride, reg);
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, img, target, out, L_pred) && ((uintptr_t)L_target % 16 == 0);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1)), bpi = (n + 255u) / 256u;  // <= the blocks the scratch is sized for
-  if ((uint64_t)bpi * (uint64_t)B > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, img, target, out, L_pred, L_target));  // p.bpi <= the blocks the scratch is sized for
+  if (p.too_large()) return fail(CURL_E_SHAPE, "grid too large");
   // small launches collapse their curves inside the kernel (one launch less: launch_stream's rule and CURL_F_TUNE_PREP)
   const unsigned psel = (flags & CURL_F_TUNE_PREP_MASK) >> CURL_F_TUNE_PREP_SHIFT;
-  const bool self_prep = psel == 2 || (psel == 0 && (uint64_t)bpi * (uint64_t)B <= kSelfPrepMaxTiles);
+  const bool self_prep = psel == 2 || (psel == 0 && (uint64_t)p.bpi * (uint64_t)B <= kSelfPrepMaxTiles);
   if (!self_prep)
-    if (int rc = launch_prep(prep, B, s)) return rc;
+    if (int rc = launch_prep(k.prep, B, s)) return rc;
   LayerLossArgs a;
-  a.img = img, a.tgt = target, a.mask = mask_kind ? mask : nullptr, a.coef = ws, a.out = out, a.partial = (float*)scratch;
-  a.Lp = L_pred, a.Lt = L_target, a.coef_stride = stride, a.n = n, a.blocks_per_image = bpi;
-  dim3 grid(bpi, (unsigned)B), block(256);
-#define LAUNCH_LAYER_LOSS(V, M)                                                                       \
-  do {                                                                                                \
-    if (self_prep) hipLaunchKernelGGL((layer_loss_kernel<V, M, true>), grid, block, 0, s, a, prep);   \
-    else hipLaunchKernelGGL((layer_loss_kernel<V, M, false>), grid, block, 0, s, a, prep);            \
-  } while (0)
-  DISPATCH_VEC_MASK(LAUNCH_LAYER_LOSS, aligned, mask_kind);
-#undef LAUNCH_LAYER_LOSS
-  hipLaunchKernelGGL(loss_terms_final_kernel, dim3((unsigned)B), dim3(LOSS_FINAL_THREADS), 0, s, (const float*)scratch, sums, bpi);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "layer_loss kernels");
-  return 0;
+  a.img = img, a.tgt = target, a.mask = mask_kind ? mask : nullptr, a.coef = k.ws, a.out = out, a.partial = (float*)scratch;
+  a.Lp = L_pred, a.Lt = L_target, a.coef_stride = k.stride, a.n = p.n, a.blocks_per_image = p.bpi;
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    if (self_prep) hipLaunchKernelGGL((layer_loss_kernel<V, M, true>), p.grid, dim3(256), 0, s, a, k.prep);
+    else hipLaunchKernelGGL((layer_loss_kernel<V, M, false>), p.grid, dim3(256), 0, s, a, k.prep);
+  });
+  hipLaunchKernelGGL(loss_terms_final_kernel, dim3((unsigned)B), dim3(LOSS_FINAL_THREADS), 0, s, (const float*)scratch, sums, p.bpi);
+  return hip_done("layer_loss kernels");
 }
 
 // `weights` is a DEVICE pointer: the host cannot look at it.  Supported: any finite float32 for the three L1 weights (0, 2, 3) --
@@ -1403,24 +1302,18 @@ int curl_loss_terms_bwd_f32(const float* pred, const float* target, const void* 
   if (!weights || !grad_pred) return fail(CURL_E_NULL, "weights / grad_pred is NULL");
   if (int rc = check_mask(mask, mask_kind)) return rc;
   const size_t HW = (size_t)H * W;
-  const bool aligned = planes_vec4(HW, mask, mask_kind, pred, target, grad_L_pred, grad_pred);
-  const unsigned n = (unsigned)(HW / (aligned ? 4 : 1)), bpi = (n + 255u) / 256u;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(bpi, (unsigned)B), block(256);
-#define LAUNCH_LOSS_BWD(V, M) \
-  hipLaunchKernelGGL((loss_terms_bwd_kernel<V, M>), grid, block, aux_lds(kResLossBwd, grid, V == 4, 0), s, pred, target, mask, weights, grad_L_pred, grad_pred, n)
-  DISPATCH_VEC_MASK(LAUNCH_LOSS_BWD, aligned, mask_kind);
-#undef LAUNCH_LOSS_BWD
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "loss_terms_bwd_kernel");
-  return 0;
+  const Pointwise p = pointwise(HW, B, planes_vec4(HW, mask, mask_kind, 16, pred, target, grad_L_pred, grad_pred));
+  dispatch_vec_mask<kMasksAll>(p.aligned, mask_kind, [&](auto V, auto M) {
+    hipLaunchKernelGGL((loss_terms_bwd_kernel<V, M>), p.grid, dim3(256), aux_lds(kResLossBwd, p.grid, V == 4, 0), (hipStream_t)stream, pred, target,
+                       mask, weights, grad_L_pred, grad_pred, p.n);
+  });
+  return hip_done("loss_terms_bwd_kernel");
 }
 
 size_t curl_trispace_bwd_scratch_bytes(int B, int H, int W, int num_coeffs) {
   if (B <= 0 || H <= 0 || W <= 0 || (num_coeffs != 126 && num_coeffs != 35)) return 0;
   size_t HW = (size_t)H * W;
-  size_t tiles = (num_coeffs == 126 && kTriBwdStrips) ? strip_geo(B, H, W).tiles() : tri_tiles(B, HW);
-  return ((size_t)B * 18 * HW + (size_t)B * tiles * 9 * num_coeffs) * sizeof(float);
+  return ((size_t)B * 18 * HW + (size_t)B * tri_bwd_tiles(B, H, W, num_coeffs) * 9 * num_coeffs) * sizeof(float);
 }
 
 int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* grad_out, float* grad_coeffs, void* scratch,
@@ -1429,24 +1322,21 @@ int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* gr
   g_err[0] = 0;
   if (int rc = check_img(img, grad_out, B, H, W)) return rc;
   if (!coeffs || !grad_coeffs) return fail(CURL_E_NULL, "coeffs / grad_coeffs is NULL");
-  if (num_coeffs != 126 && num_coeffs != 35) return fail(CURL_E_KNOTS, "num_coeffs must be 126 or 35");
+  if (int rc = check_num_coeffs(num_coeffs, "num_coeffs must be 126 or 35")) return rc;
   if (int rc = check_flags(flags, CURL_F_RESIDUAL_ONLY)) return rc;
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
-  if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_trispace_bwd_scratch_bytes(B, H, W, num_coeffs))
-    return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_trispace_bwd_scratch_bytes");
+  if (int rc = check_scratch(scratch, scratch_bytes, curl_trispace_bwd_scratch_bytes(B, H, W, num_coeffs), true,
+                             "scratch missing, misaligned or smaller than curl_trispace_bwd_scratch_bytes"))
+    return rc;
   size_t HW = (size_t)H * W;
-  {  // the accumulation pass is a 1-D grid of (image, space, tile, chunk) blocks
-    const uint64_t tiles = (num_coeffs == 126 && kTriBwdStrips) ? strip_geo(B, H, W).tiles() : tri_tiles(B, HW);
-    if ((uint64_t)B * 3u * tiles * 3u + 64u > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
-  }
+  // the accumulation pass is a 1-D grid of (image, space, tile, chunk) blocks
+  if ((uint64_t)B * 3u * tri_bwd_tiles(B, H, W, num_coeffs) * 3u + 64u > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
   float* pxbuf = (float*)scratch;
   float* partial = pxbuf + (size_t)B * 18 * HW;
   int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
-  hipError_t e = (num_coeffs == 126)
-                     ? launch_trispace_bwd<5>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream)
-                     : launch_trispace_bwd<3>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "trispace backward kernels");
-  return 0;
+  if (num_coeffs == 126) launch_trispace_bwd<5>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
+  else launch_trispace_bwd<3>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
+  return hip_done("trispace backward kernels");
 }
 
 size_t curl_poly_layer_bwd_scratch_bytes(int B, int H, int W, int num_variables) {
@@ -1462,12 +1352,13 @@ int curl_poly_layer_bwd_f32(const float* img, const float* coeffs, const float* 
   if (int rc = check_img(img, grad_out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
   if (!grad_img && !grad_coeffs) return fail(CURL_E_NULL, "grad_img and grad_coeffs are both NULL: nothing to compute");
-  if (num_variables != 5 && num_variables != 3) return fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)");
+  if (int rc = check_num_variables(num_variables)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (flags must be 0)");
   const size_t HW = (size_t)H * W;
   if (grad_coeffs) {  // the tile partials; the image gradient alone needs no scratch
-    if (!scratch || (uintptr_t)scratch % 16 || scratch_bytes < curl_poly_layer_bwd_scratch_bytes(B, H, W, num_variables))
-      return fail(CURL_E_WORKSPACE, "scratch missing, misaligned or smaller than curl_poly_layer_bwd_scratch_bytes");
+    if (int rc = check_scratch(scratch, scratch_bytes, curl_poly_layer_bwd_scratch_bytes(B, H, W, num_variables), true,
+                               "scratch missing, misaligned or smaller than curl_poly_layer_bwd_scratch_bytes"))
+      return rc;
     // a 1-D grid of (image, tile, chunk) blocks
     if ((uint64_t)B * poly_bwd_tiles(B, HW) * 3u + 64u > 0x7fffffffull) return fail(CURL_E_SHAPE, "grid too large");
   }
@@ -1475,9 +1366,7 @@ int curl_poly_layer_bwd_f32(const float* img, const float* coeffs, const float* 
     launch_poly_layer_bwd<5>(img, coeffs, grad_out, grad_img, grad_coeffs, (float*)scratch, B, HW, (hipStream_t)stream);
   else
     launch_poly_layer_bwd<3>(img, coeffs, grad_out, grad_img, grad_coeffs, (float*)scratch, B, HW, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "poly_layer backward kernels");
-  return 0;
+  return hip_done("poly_layer backward kernels");
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ Four clocks per shape, because a 10-20 us step is as much host as device:
   cabi_us     the same window with the C ABI called directly on preallocated buffers (no tensor allocation, no checks)
   latency_us  one call between two events after a device sync (what a caller issuing ONE call sees)
 
-    python tools/small_batch.py [--flags-fwd N] [--flags-bwd N]
+    python tools/small_batch.py [--flags-fwd N] [--flags-bwd N] [--shapes 32x256x256,1x256x256]
 """
 import argparse
 import os
@@ -26,6 +26,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--flags-fwd", type=lambda s: int(s, 0), default=0)
 ap.add_argument("--flags-bwd", type=lambda s: int(s, 0), default=0)
 ap.add_argument("--n", type=int, default=400)
+ap.add_argument("--shapes", default="1x1000x1500,2x1000x1500,4x1000x1500,32x256x256,32x1000x1500",
+                help="comma-separated BxHxW (a host-cost A/B of two builds looks at the small ones only)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 lib = _lib.load()
@@ -60,7 +62,7 @@ def latency(fn, n=40):
 
 
 print(f"{'shape':>16s} {'pass':>5s} {'window_us':>10s} {'host_us':>8s} {'cabi_us':>8s} {'cabi_host':>9s} {'latency_us':>10s}")
-for (B, H, W) in ((1, 1000, 1500), (2, 1000, 1500), (4, 1000, 1500), (32, 256, 256), (32, 1000, 1500)):
+for (B, H, W) in (tuple(int(v) for v in shape.split("x")) for shape in args.shapes.split(",")):
     torch.manual_seed(0)
     imgs = [torch.rand(B, 3, H, W, device=dev) for _ in range(2)]
     gout = torch.rand(B, 3, H, W, device=dev)
