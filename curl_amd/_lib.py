@@ -94,6 +94,12 @@ SIGNATURES = {
     "curl_compose_white_u8hwc": (_i, [_c_f, _c_f, _i, _c_f, _i, _i, _i, _c_f]),
 }
 
+# include/curl_hip_grad.h: the entry points declared beside curl_hip.h (bound by load() with the table above; a table of its
+# own because tests/test_abi.py holds SIGNATURES to curl_hip.h's declarations)
+SIGNATURES_GRAD = {
+    "curl_trispace_bwd_img_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),
+}
+
 _lib = None
 
 
@@ -116,7 +122,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "../../include/curl_hip.h"
+#include "../../include/curl_hip_grad.h"
 #include "curl_math_bwd.h"
 #include "curl_math_poly.h"
 #include "curl_math_loss.h"
@@ -209,6 +210,8 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/msssim.inc"
 #include "kernels/poly_bwd.inc"
 #include "kernels/poly_layer_bwd.inc"
+#include "kernels/trispace_img_grad.inc"
 #include "kernels/loss.inc"
 #include "kernels/edges.inc"
 #include "kernels/host_api.inc"
+#include "kernels/host_api_grad.inc"

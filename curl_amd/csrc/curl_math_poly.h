@@ -554,4 +554,121 @@ CURL_HD void poly_img_grad_n(float (&gin)[V][N], const float (&vars)[V][N], cons
     }
 }
 
+// ---------------------------------------------------------------- image gradient of the fused polynomial model
+// d loss / d img of trispace_n (model.py:499-520), the coordinates being data.  With v_s = (rgb, rgb2lab(rgb), rgb2hsv(rgb)):
+//   g_P[s][o]  as trispace_bwd_n forms it (clamp gate, 2(. - 1/2), the back-converters' pullbacks, sigma')
+//   g_v[s][i]  = sum_o g_P[s][o] * dP_{s,o}/dv_i(v_s, x, y)        i = the three colour variables
+//   g_img      = g_v[0] + rgb2lab_pull(g_v[1]) + rgb2hsv_pull(g_v[2]) + the gated g of generate_image's identity term
+// One table per image, in the order the Horner schemes consume it: the 9 forward polynomials (kSeqStride apart, as the
+// forward kernel stages them), then per space the 9 derivative polynomials [i][o] of poly_deriv_stage's first three variables.
+template <int V>
+struct TriImgGrad {
+  static constexpr int kFwd = 9 * PolyEval<V>::kSeqStride, kDerSpace = 9 * PolyDeriv<V>::kTerms;
+  static constexpr int kFloats = kFwd + 3 * kDerSpace;  // 2 664 (V = 5), 864 (V = 3)
+};
+// entry j of that table; coef = [3][3][NC] of the image, reference order
+template <int V>
+CURL_HD float trispace_img_grad_stage(const float* coef, int j) {
+  constexpr int NC = PolyEval<V>::kCoeffs, NS = PolyEval<V>::kSeqStride;
+  if (j < TriImgGrad<V>::kFwd) {
+    const int q = j / NS, pos = j - q * NS;
+    return pos < NC ? coef[q * NC + PolyEval<V>::order(pos)] : 0.0f;  // (padding slots are never read)
+  }
+  j -= TriImgGrad<V>::kFwd;
+  const int s = j / TriImgGrad<V>::kDerSpace;
+  return poly_deriv_stage<V>(coef + s * 3 * NC, j - s * TriImgGrad<V>::kDerSpace);
+}
+// The N pixels of a lane in lock step through every polynomial (scalar chains sharing each coefficient read, as
+// poly_img_grad_n); the converters one pixel at a time.  rgb2lab's tape (6 floats) is kept from the forward sweep, rgb2hsv's
+// (13 lane predicates: N of them do not fit the SGPR file) is formed again where its pullback runs -- two reciprocals.
+template <int V, int N>
+CURL_HD void trispace_img_grad_n(const PxN<N>& in, const float (&xw)[N], const float (&yh)[N], const float* tab,
+                                 const PxN<N>& gout, bool residual_only, PxN<N>& gin) {
+  constexpr int NS = PolyEval<V>::kSeqStride, NT = PolyDeriv<V>::kTerms;
+  const float* D = tab + TriImgGrad<V>::kFwd;
+  Rgb2LabT t_lab[N];
+  float vs[3][N][V], sig[3][3][N], rs[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    const Px p{in.c0[e], in.c1[e], in.c2[e]};
+    Rgb2HsvT t_hsv;
+    const Px sp[3] = {p, rgb2lab_t(p, t_lab[e]), rgb2hsv_t(p, t_hsv)};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      vs[s][e][0] = sp[s].c0, vs[s][e][1] = sp[s].c1, vs[s][e][2] = sp[s].c2;
+      if constexpr (V == 5) vs[s][e][3] = xw[e], vs[s][e][4] = yh[e];
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {  // forward recompute
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+      CURL_FENCE();
+      PolyEval<V>::template eval<float, true, N>(rs, vs[s], tab + (s * 3 + o) * NS);
+#pragma unroll
+      for (int e = 0; e < N; ++e) sig[s][o][e] = rs[e];
+    }
+    CURL_FENCE();
+    float flat[3 * N];
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+      for (int e = 0; e < N; ++e) flat[o * N + e] = sig[s][o][e];
+    sigmoid_run(flat);
+#pragma unroll
+    for (int o = 0; o < 3; ++o)
+#pragma unroll
+      for (int e = 0; e < N; ++e) sig[s][o][e] = flat[o * N + e];
+  }
+  float gid[3][N];  // the identity term's gated gradient (generate_image); sig becomes g_P in place
+#pragma unroll
+  for (int e = 0; e < N; ++e) {  // as trispace_bwd_n
+    const Px s1{sig[1][0][e], sig[1][1][e], sig[1][2][e]}, s2{sig[2][0][e], sig[2][1][e], sig[2][2][e]};
+    Px g_res{gout.c0[e], gout.c1[e], gout.c2[e]};
+    Lab2RgbT t1;
+    Hsv2RgbT t2;
+    const Px y1 = lab2rgb_t(s1, t1), y2 = hsv2rgb_t<false>(s2, t2);
+    if (!residual_only) {  // generate_image: clamp(img + residual, 0, 1)
+      const float r0 = 2.0f * (sig[0][0][e] - 0.5f) + 2.0f * (y1.c0 - 0.5f) + 2.0f * (y2.c0 - 0.5f);
+      const float r1 = 2.0f * (sig[0][1][e] - 0.5f) + 2.0f * (y1.c1 - 0.5f) + 2.0f * (y2.c1 - 0.5f);
+      const float r2 = 2.0f * (sig[0][2][e] - 0.5f) + 2.0f * (y1.c2 - 0.5f) + 2.0f * (y2.c2 - 0.5f);
+      g_res = Px{g_res.c0 * pass01(in.c0[e] + r0), g_res.c1 * pass01(in.c1[e] + r1), g_res.c2 * pass01(in.c2[e] + r2)};
+      gid[0][e] = g_res.c0, gid[1][e] = g_res.c1, gid[2][e] = g_res.c2;
+    } else {
+      gid[0][e] = gid[1][e] = gid[2][e] = 0.0f;
+    }
+    const Px gy{2.0f * g_res.c0, 2.0f * g_res.c1, 2.0f * g_res.c2};
+    const Px gs[3] = {gy, lab2rgb_pull(t1, gy), hsv2rgb_pull<false>(t2, gy)};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      sig[s][0][e] = gs[s].c0 * sig[s][0][e] * (1.0f - sig[s][0][e]);
+      sig[s][1][e] = gs[s].c1 * sig[s][1][e] * (1.0f - sig[s][1][e]);
+      sig[s][2][e] = gs[s].c2 * sig[s][2][e] * (1.0f - sig[s][2][e]);
+    }
+  }
+  float gv[3][3][N];
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int o = 0; o < 3; ++o) {
+        CURL_FENCE();
+        PolyDeriv<V>::template eval<float, true, N>(rs, vs[s], D + ((s * 3 + i) * 3 + o) * NT);
+#pragma unroll
+        for (int e = 0; e < N; ++e) gv[s][i][e] = o == 0 ? sig[s][0][e] * rs[e] : poly_fmav(sig[s][o][e], rs[e], gv[s][i][e]);
+      }
+  CURL_FENCE();
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    Rgb2HsvT t_hsv;
+    rgb2hsv_t(Px{in.c0[e], in.c1[e], in.c2[e]}, t_hsv);
+    const Px gl = rgb2lab_pull(t_lab[e], Px{gv[1][0][e], gv[1][1][e], gv[1][2][e]});
+    const Px gh = rgb2hsv_pull(t_hsv, Px{gv[2][0][e], gv[2][1][e], gv[2][2][e]});
+    gin.c0[e] = ((gv[0][0][e] + gl.c0) + gh.c0) + gid[0][e];
+    gin.c1[e] = ((gv[0][1][e] + gl.c1) + gh.c1) + gid[1][e];
+    gin.c2[e] = ((gv[0][2][e] + gl.c2) + gh.c2) + gid[2][e];
+  }
+}
+
 }  // namespace curlm

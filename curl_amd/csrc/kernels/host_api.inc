@@ -697,7 +697,7 @@ extern "C" {
 // 0.1.9: backward entry points of the stand-alone curve ops, converters and fused stages (curl_*_bwd_f32)
 // 0.1.10: curl_layer_pwl_bwd_f32, the fused layer's backward with the paper's piecewise-linear curves (CURL_F_PWL)
 // 0.1.11: curl_poly_layer_bwd_f32, the stand-alone polynomial layers' backward (image and coefficient gradients)
-int curl_version(void) { return 111; }
+int curl_version(void) { return 112; }
 
 const char* curl_last_error(void) { return g_err; }
 

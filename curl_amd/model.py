@@ -316,7 +316,8 @@ def _powers(degree, num_variables):
 
 
 class _TriSpaceFn(torch.autograd.Function):
-    """Autograd node around the fused polynomial kernels: gradient w.r.t. the coefficients only."""
+    """Autograd node around the fused polynomial kernels: forward = ops.trispace_forward; backward = ops.trispace_backward
+    (coefficients) and ops.trispace_backward_img (image), each launched only when its gradient is needed."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -327,12 +328,13 @@ class _TriSpaceFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         img, coeffs = ctx.saved_tensors
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("curl_amd: the polynomial path differentiates w.r.t. the coefficients only "
-                                      "(the image is data in main.py's train step)")
-        return None, ops.trispace_backward(img, coeffs, grad_out.contiguous(), ctx.residual_only), None
+        grad_out = grad_out.contiguous()
+        g_img = ops.trispace_backward_img(img, coeffs, grad_out, ctx.residual_only) if ctx.needs_input_grad[0] else None
+        g_coeffs = ops.trispace_backward(img, coeffs, grad_out, ctx.residual_only) if ctx.needs_input_grad[1] else None
+        return g_img, g_coeffs, None
 
 
 class _PolyLayerFn(torch.autograd.Function):
@@ -478,10 +480,10 @@ class TriSpaceRegNet(nn.Module):
         return coeffs[:, 0], coeffs[:, 1], coeffs[:, 2]
 
     def generate_residual(self, img, R, L, H):
-        """model.py:499-515, one kernel (differentiable w.r.t. R, L, H)."""
+        """model.py:499-515, one kernel (differentiable w.r.t. R, L, H and the image)."""
         self._check_resolution(img)  # model.py:491
         coeffs = torch.stack((R, L, H), 1)
-        if torch.is_grad_enabled() and coeffs.requires_grad:
+        if torch.is_grad_enabled() and (coeffs.requires_grad or img.requires_grad):
             return _TriSpaceFn.apply(img, coeffs, True)
         return ops.trispace_forward(img, coeffs, residual_only=True)
 
@@ -496,7 +498,7 @@ class TriSpaceRegNet(nn.Module):
         coeffs = self.backbone(img * mask).reshape(img.shape[0], self.num_spaces, self.num_channels, self.num_coeffs)
         input_img = img if target_img is None else target_img
         self._check_resolution(input_img)  # model.py:491
-        if torch.is_grad_enabled() and coeffs.requires_grad:
+        if torch.is_grad_enabled() and (coeffs.requires_grad or input_img.requires_grad):
             return _TriSpaceFn.apply(input_img, coeffs, not self.is_train)
         return ops.trispace_forward(input_img, coeffs, residual_only=not self.is_train)
 

@@ -760,6 +760,28 @@ def trispace_backward(img, coeffs, grad_out, residual_only=False):
     return g
 
 
+TRISPACE_IMG_GRAD_TILE = 4096  # pixels per workgroup of trispace_backward_img's float4 kernel (256 lanes x 4 pixels x 4 steps)
+
+
+@_one_device
+@_empty_ok()
+def trispace_backward_img(img, coeffs, grad_out, residual_only=False):
+    """d loss / d img [B,3,H,W] of trispace_forward, given grad_out = d loss / d out (include/curl_hip_grad.h): one per-pixel
+    pass, no scratch.  The coordinates of the spatial form are data."""
+    lib = _lib.load()
+    img, grad_out = _image(img), _image(grad_out, "grad_out")
+    B, _, H, W = img.shape
+    if grad_out.shape != img.shape:
+        raise ValueError(f"grad_out must have img's shape {tuple(img.shape)}, got {tuple(grad_out.shape)}")
+    _check_coeffs(coeffs, B)
+    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
+    g = torch.empty_like(img)
+    rc = lib.curl_trispace_bwd_img_f32(img.data_ptr(), c.data_ptr(), grad_out.data_ptr(), g.data_ptr(), B, H, W, c.shape[3],
+                                       _lib.F_RESIDUAL_ONLY if residual_only else 0, _stream(img))
+    _lib.check(rc, "curl_trispace_bwd_img_f32")
+    return g
+
+
 def _poly_layer_args(img, coeffs):
     """The stand-alone polynomial layer's tensor checks: img float32 [B,3|5,H,W], coeffs [B,3,35|126]."""
     _need_device(img, "img")
