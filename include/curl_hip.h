@@ -15,6 +15,12 @@
  *   - work is enqueued on `stream` (a hipStream_t passed as void*; 0 = default stream)
  *     and the call returns without synchronising;
  *   - re-entrant, no global mutable state; the error string is thread-local;
+ *   - no byte outside the documented extent of a buffer is written, and none outside it reaches a result: a workspace or
+ *     scratch buffer of exactly the bytes its *_bytes function returns is enough, at any alignment the entry accepts; an
+ *     output documented as ASSIGNED is written in full; a nullable output passed as NULL is skipped
+ *     (tests/test_gpu_guard_bands.py holds every entry point to this between poisoned guard bands).  With `reg` NULL the
+ *     other outputs of the adjust_*, stage, layer (f32, slab, u8hwc) and layer_loss forwards are the same bits as with it;
+ *     what grad_img == NULL does to the knot gradients is said at curl_layer_bwd_f32 (equal within an ulp of the sums);
  *   - return value: 0 = ok; <0 = argument error (CURL_E_*); >0 = a hipError_t.
  *     No exception crosses the boundary and nothing calls exit().
  *
@@ -97,7 +103,9 @@ enum {
                                             Forward: curl_layer_fwd(_slab)_f32, curl_lab_stage_f32, curl_hsv_stage_f32,
                                             curl_adjust_*_f32 (affine form).  Results are bit-identical either way. */
 #define CURL_F_DIAG_NO_MEM 0x10000u   /* DIAGNOSTICS ONLY: inputs synthesised in registers, stores suppressed --
-                                         times the arithmetic alone; the output buffer is left untouched */
+                                         times the arithmetic alone; the output buffer is left untouched, byte for byte
+                                         (curl_layer_fwd_f32: `out` keeps what it held; the knot prep still runs as a launch
+                                         of its own, so `reg` and the workspace are written as without the flag) */
 
 #define CURL_F_WS_READY 0x40000u /* curl_layer_bwd_f32 (and the stage backward entries): `workspace` is the buffer curl_layer_fwd_f32 (or an earlier backward) was
                                     handed for the SAME raw knots and has not been written since: it already holds the
@@ -108,7 +116,8 @@ enum {
                                     that the VALUES belong to these knots remains the caller's word */
 #define CURL_F_DIAG_SKIP_PREP 0x20000u /* DIAGNOSTICS ONLY (curl_layer_fwd_f32): the knot-prep launch is skipped and the
                                          workspace is taken to hold an earlier call's result for the same knots; `reg`
-                                         is not written.  Measures what the prep launch + its kernel boundary cost. */
+                                         is not written (it keeps what it held, byte for byte); `out` is the plain call's,
+                                         bit for bit.  Measures what the prep launch + its kernel boundary cost. */
 
 int curl_version(void);
 /* Thread-local description of the last non-zero return on this thread ("" if none). */
