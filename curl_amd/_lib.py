@@ -27,6 +27,18 @@ F_WS_READY = 0x40000
 F_MASK_FIRST = 0x400000  # foreground masks: fully masked-out wavefronts never read their pixels
 MAX_KNOTS = 256
 
+
+def poly_vars(num_variables, degree):
+    """include/curl_hip_poly.h CURL_POLY_VARS(V, degree): curl_poly_layer_f32's num_variables with the polynomial degree in the
+    high 16 bits (a plain V is degree 4; degree 0 packs a value the library refuses)."""
+    return num_variables | ((degree if degree > 0 else 0x7fff) << 16)
+
+
+def poly_coeffs(num_coeffs, order):
+    """include/curl_hip_poly.h CURL_POLY_COEFFS(num_coeffs, order): the curl_trispace_fwd_* entries' num_coeffs with the
+    polynomial order in the high 16 bits (a plain 126 | 35 is order 4)."""
+    return num_coeffs | ((order if order > 0 else 0x7fff) << 16)
+
 _c_f = ctypes.c_void_p  # device pointers travel as integers
 _i = ctypes.c_int
 _u = ctypes.c_uint

@@ -3,7 +3,8 @@
 // generate_image (model.py:499-520).  Same dual compilation as curl_math.h.
 //
 // Per pixel and colour space: 3 outputs, each a polynomial of total degree <= 4 in V = 5 variables (3 colour
-// channels + x/W + y/H; 126 coefficients) or V = 3 (35).  Evaluated in multivariate Horner form
+// channels + x/W + y/H; 126 coefficients) or V = 3 (35); orders 1-3 (56 | 20, 21 | 10, 6 | 4 coefficients) have Horner
+// schemes and forward kernels of their own (PolyEval<V, D>).  Evaluated in multivariate Horner form
 // (poly_horner.inc, generated): 125 FMAs per output instead of 121 shared multiplies + 126 FMAs.  On gfx950
 // the value type is a packed pair of pixels (v_pk_fma_f32) and the coefficients are wave-uniform: they are
 // read through a uniform pointer, i.e. scalar loads into SGPRs that feed the packed FMAs directly.
@@ -96,10 +97,13 @@ struct PolyCoef<curl_f2> {
 #undef CURL_POLY_FMA
 #undef CURL_POLY_FMAV
 
-template <int V>
+// D = the polynomial order (total degree).  Order 4 carries everything the backward kernels use (chunked monomials); orders
+// 1-3 are forward-only: the graded monomial order makes an order-D table the first kCoeffs entries of the order-4 one, so their
+// gradients come from the order-4 kernels on the zero-padded table (include/curl_hip.h).
+template <int V, int D = 4>
 struct PolyEval;
 template <>
-struct PolyEval<5> {
+struct PolyEval<5, 4> {
   static constexpr int kCoeffs = 126;
   static constexpr int kSeqStride = 128;  // floats per polynomial in the consumption-order (LDS) layout: 16-byte multiple
   template <class F, bool SEQ, int NP>
@@ -110,7 +114,7 @@ struct PolyEval<5> {
   static CURL_HD void monomials(float (&m)[42], const float (&pw)[5][5]) { mono_d4_v5<C>(m, pw); }
 };
 template <>
-struct PolyEval<4> {  // 3 colour channels + x/W: the per-row collapsed form of the 5-variable polynomial (below)
+struct PolyEval<4, 4> {  // 3 colour channels + x/W: the per-row collapsed form of the 5-variable polynomial (below)
   static constexpr int kCoeffs = 70;
   static constexpr int kSeqStride = 72;
   template <class F, bool SEQ, int NP>
@@ -121,7 +125,7 @@ struct PolyEval<4> {  // 3 colour channels + x/W: the per-row collapsed form of 
   static CURL_HD void monomials(float (&m)[35], const float (&pw)[4][5]) { mono_d4_v4<C>(m, pw); }
 };
 template <>
-struct PolyEval<3> {
+struct PolyEval<3, 4> {
   static constexpr int kCoeffs = 35;
   static constexpr int kSeqStride = 36;
   template <class F, bool SEQ, int NP>
@@ -132,13 +136,32 @@ struct PolyEval<3> {
   static CURL_HD void monomials(float (&m)[35], const float (&pw)[3][5]) { mono_d4_v3<C>(m, pw); }
 };
 
+// orders 1-3: kCoeffs = C(V + D, D); kSeqStride = kCoeffs rounded up to a 16-byte multiple (PolyCoef<curl_f2>::pair reads the
+// aligned group of four around a coefficient)
+#define POLY_LOW_ORDER(V, D, NCOEF)                                                                                 \
+  template <>                                                                                                       \
+  struct PolyEval<V, D> {                                                                                           \
+    static constexpr int kCoeffs = NCOEF;                                                                           \
+    static constexpr int kSeqStride = (NCOEF + 3) & ~3;                                                             \
+    template <class F, bool SEQ, int NP>                                                                            \
+    static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][V], const float* c) { poly_d##D##_v##V<F, SEQ, NP>(out, v, c); } \
+    static CURL_HD int order(int pos) { return kPolyOrder_d##D##_v##V[pos]; }                                       \
+  };
+POLY_LOW_ORDER(5, 3, 56)
+POLY_LOW_ORDER(5, 2, 21)
+POLY_LOW_ORDER(5, 1, 6)
+POLY_LOW_ORDER(3, 3, 20)
+POLY_LOW_ORDER(3, 2, 10)
+POLY_LOW_ORDER(3, 1, 4)
+#undef POLY_LOW_ORDER
+
 // out[o][i] = P_o(vars[.][i]) for the N pixels of a lane; coef = [3][NC] of one image and one space, in the
 // reference's order (SEQ = false) or permuted into Horner consumption order (SEQ = true).  vars is plane-major.
-template <int V, int N, bool SEQ = false>
+template <int V, int N, bool SEQ = false, int D = 4>
 CURL_HD void poly3_n(float (&out)[3][N], const float (&vars)[V][N], const float* coef) {
   // SEQ layout: every polynomial starts on a 16-byte boundary (kSeqStride), so the sequential reads merge into
   // ds_read_b64 / b128 with 16-bit offsets instead of ds_read2_b32 pairs that need a fresh base register every 1 KB
-  constexpr int NC = SEQ ? PolyEval<V>::kSeqStride : PolyEval<V>::kCoeffs;
+  constexpr int NC = SEQ ? PolyEval<V, D>::kSeqStride : PolyEval<V, D>::kCoeffs;
 #if defined(__HIP_DEVICE_COMPILE__)
   // One output polynomial at a time, all pixel pairs of the lane in lock step (poly_horner.inc): the pairs share
   // every coefficient read (one broadcast ds_read_b128 feeds 4 terms x N/2 packed FMAs) and are the ILP of the
@@ -157,7 +180,7 @@ CURL_HD void poly3_n(float (&out)[3][N], const float (&vars)[V][N], const float*
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
       CURL_FENCE();
-      PolyEval<V>::template eval<curl_f2, SEQ, NP>(r, v, coef + o * NC);
+      PolyEval<V, D>::template eval<curl_f2, SEQ, NP>(r, v, coef + o * NC);
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
         out[o][2 * q] = r[q].x;
@@ -172,7 +195,7 @@ CURL_HD void poly3_n(float (&out)[3][N], const float (&vars)[V][N], const float*
     for (int k = 0; k < V; ++k) vs[0][k] = vars[k][N - 1];
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
-      PolyEval<V>::template eval<float, SEQ, 1>(rs, vs, coef + o * NC);
+      PolyEval<V, D>::template eval<float, SEQ, 1>(rs, vs, coef + o * NC);
       out[o][N - 1] = rs[0];
     }
   }
@@ -181,7 +204,7 @@ CURL_HD void poly3_n(float (&out)[3][N], const float (&vars)[V][N], const float*
     float v[1][V], r[1];
     for (int k = 0; k < V; ++k) v[0][k] = vars[k][i];
     for (int o = 0; o < 3; ++o) {
-      PolyEval<V>::template eval<float, SEQ, 1>(r, v, coef + o * NC);
+      PolyEval<V, D>::template eval<float, SEQ, 1>(r, v, coef + o * NC);
       out[o][i] = r[0];
     }
   }
@@ -209,9 +232,9 @@ CURL_HD void sigmoid_run(float (&x)[M]) {
 // TriSpaceRegNet.generate_residual (model.py:499-515) [+ generate_image (model.py:517-520) unless residual_only]
 // for the N pixels of a lane.  p: RGB in, result out.  xw, yh: x/width and y/height of each pixel
 // (cat_coords, model.py:487-497; unused when V == 3).  coef: [3 spaces = R, L, H][3][NC] of this image.
-template <int V, int N, bool SEQ = false>
+template <int V, int N, bool SEQ = false, int D = 4>
 CURL_HD void trispace_n(PxN<N>& p, const float (&xw)[N], const float (&yh)[N], const float* coef, bool residual_only) {
-  constexpr int NC = SEQ ? PolyEval<V>::kSeqStride : PolyEval<V>::kCoeffs;
+  constexpr int NC = SEQ ? PolyEval<V, D>::kSeqStride : PolyEval<V, D>::kCoeffs;
   PxN<N> lab = p, hsv = p;
   rgb2lab_n<N, kPolySel>(lab);
   rgb2hsv_n<N>(hsv);
@@ -241,7 +264,7 @@ CURL_HD void trispace_n(PxN<N>& p, const float (&xw)[N], const float (&yh)[N], c
   };
   // RGB space: rgb_res = sigmoid(poly(cat(rgb, x, y), R)); 2 * (rgb_res - 0.5)
   fill(p);
-  poly3_n<V, N, SEQ>(o, vars, coef);
+  poly3_n<V, N, SEQ, D>(o, vars, coef);
   squash();
 #pragma unroll
   for (int c = 0; c < 3; ++c)
@@ -249,7 +272,7 @@ CURL_HD void trispace_n(PxN<N>& p, const float (&xw)[N], const float (&yh)[N], c
     for (int i = 0; i < N; ++i) res[c][i] = 2.0f * (o[c][i] - 0.5f);
   // Lab space: lab2rgb(sigmoid(poly(cat(lab, x, y), L)))
   fill(lab);
-  poly3_n<V, N, SEQ>(o, vars, coef + 3 * NC);
+  poly3_n<V, N, SEQ, D>(o, vars, coef + 3 * NC);
   squash();
   {
     PxN<N> q;
@@ -265,7 +288,7 @@ CURL_HD void trispace_n(PxN<N>& p, const float (&xw)[N], const float (&yh)[N], c
   }
   // HSV space: hsv2rgb(sigmoid(poly(cat(hsv, x, y), H)))
   fill(hsv);
-  poly3_n<V, N, SEQ>(o, vars, coef + 6 * NC);
+  poly3_n<V, N, SEQ, D>(o, vars, coef + 6 * NC);
   squash();
 #pragma unroll
   for (int i = 0; i < N; ++i) {

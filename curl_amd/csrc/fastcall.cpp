@@ -154,6 +154,7 @@ py::object trispace_fwd_u8hwc(const at::Tensor& img, const at::Tensor& coeffs, c
     return py::none();
   const int64_t B = img.size(0), H = img.size(1), W = img.size(2);
   if (B > INT_MAX || H > INT_MAX || W > INT_MAX) return py::none();
+  // (tables of polynomial orders 1-3 -- any width but 126 | 35 -- go to the checked ctypes path, which packs their order)
   if (!plain(coeffs, at::kFloat, dev) || coeffs.dim() != 4 || coeffs.size(0) != B || coeffs.size(1) != 3 || coeffs.size(2) != 3 ||
       (coeffs.size(3) != 126 && coeffs.size(3) != 35) || (reinterpret_cast<uintptr_t>(coeffs.data_ptr()) & 7u))
     return py::none();

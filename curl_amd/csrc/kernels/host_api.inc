@@ -9,9 +9,9 @@ static int check_img(const void* in, const void* out, int B, int H, int W) {
   if (B > 65535) return fail(CURL_E_SHAPE, "B exceeds 65535 images per call");
   return 0;
 }
-// the SPATIAL polynomial tables (126 coefficients) are copied into LDS as 8-byte pairs (9 x 126 floats per image: every
-// image's table starts on an 8-byte boundary when the first one does).  The 35-coefficient forms read scalars: a float's
-// own 4-byte alignment is all they need.
+// the SPATIAL order-4 polynomial tables (126 coefficients) are copied into LDS as 8-byte pairs (9 x 126 floats per image:
+// every image's table starts on an 8-byte boundary when the first one does).  Every other width (35, and orders 1-3: 4, 10,
+// 20, 6, 21, 56) is read as scalars: a float's own 4-byte alignment is all they need.
 static int check_coeffs_aligned(const float* coeffs, int num_coeffs) {
   if (num_coeffs == 126 && (uintptr_t)coeffs % 8) return fail(CURL_E_SHAPE, "coeffs must be 8-byte aligned (num_coeffs = 126)");
   if ((uintptr_t)coeffs % 4) return fail(CURL_E_SHAPE, "coeffs must be 4-byte aligned");
@@ -419,6 +419,35 @@ static int check_num_coeffs(int num_coeffs, const char* msg) { return (num_coeff
 static int check_num_variables(int num_variables) {
   return (num_variables != 5 && num_variables != 3) ? fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)") : 0;
 }
+// The polynomial order of a forward call.  The eight coefficient counts C(V + D, D), V = 3 | 5, D = 1..4, are all different, so
+// a count names its order and its variable count; the entries still want the order said (curl_hip_poly.h packs it into the
+// high half of num_coeffs, as CURL_K_UNEVEN packs a knot count) because a plain count other than 126 | 35 has always been
+// CURL_E_KNOTS.  A high half of 0 is order 4.  -> the count, checked against the order; 0 after fail().
+static int poly_count(int V, int D) { return V == 5 ? (D == 4 ? 126 : D == 3 ? 56 : D == 2 ? 21 : 6) : (D == 4 ? 35 : D == 3 ? 20 : D == 2 ? 10 : 4); }
+static int unpack_num_coeffs(int packed, int& count, int& order) {
+  count = packed & 0xffff, order = (packed >> 16) & 0xffff;
+  if (order == 0) {
+    order = 4;
+    return check_num_coeffs(packed, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)");
+  }
+  if (order > 4 || (count != poly_count(5, order) && count != poly_count(3, order)))
+    return fail(CURL_E_KNOTS, "num_coeffs with a polynomial order in its high half: the order must be 1..4 and the count 6 | 21 | 56 | 126 (5 variables) or 4 | 10 | 20 | 35 (3 variables) for orders 1..4");
+  return 0;
+}
+// f(V, D) with both as compile-time constants, for a count unpack_num_coeffs accepted
+template <class F>
+static int dispatch_order(int count, F&& f) {
+  switch (count) {
+    case 126: return f(int_c<5>(), int_c<4>());
+    case 56: return f(int_c<5>(), int_c<3>());
+    case 21: return f(int_c<5>(), int_c<2>());
+    case 6: return f(int_c<5>(), int_c<1>());
+    case 35: return f(int_c<3>(), int_c<4>());
+    case 20: return f(int_c<3>(), int_c<3>());
+    case 10: return f(int_c<3>(), int_c<2>());
+    default: return f(int_c<3>(), int_c<1>());
+  }
+}
 
 // chain_kernel's launch in two steps, so that a caller's own launches (the knot prep, apply_curve's regulariser) come after
 // every check: the plan (verdict, tuning fields, groups per lane and LDS reservation, grid), then the launch
@@ -697,7 +726,9 @@ extern "C" {
 // 0.1.9: backward entry points of the stand-alone curve ops, converters and fused stages (curl_*_bwd_f32)
 // 0.1.10: curl_layer_pwl_bwd_f32, the fused layer's backward with the paper's piecewise-linear curves (CURL_F_PWL)
 // 0.1.11: curl_poly_layer_bwd_f32, the stand-alone polynomial layers' backward (image and coefficient gradients)
-int curl_version(void) { return 112; }
+// 0.1.13: polynomial orders 1-3: the curl_trispace_fwd_* entries take the order in the high half of num_coeffs and
+//         curl_poly_layer_f32 the degree in the high half of num_variables (include/curl_hip_poly.h)
+int curl_version(void) { return 113; }
 
 const char* curl_last_error(void) { return g_err; }
 
@@ -1006,15 +1037,22 @@ static int trispace_fwd_impl(const float* img, const float* coeffs, float* out, 
                              unsigned flags, curl_stream_t stream, Slab slab) {
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (int rc = check_num_coeffs(num_coeffs, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)")) return rc;
+  int order;
+  if (int rc = unpack_num_coeffs(num_coeffs, num_coeffs, order)) return rc;
   if (int rc = check_flags(flags, CURL_F_RESIDUAL_ONLY)) return rc;
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
   int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  if (num_coeffs == 126)
-    return launch_stream<OpTriSpaceRows>(img, out, nullptr, 0, coeffs, 9 * 126, B, H, W, flags, s, "trispace_rows", ro,
-                                         slab);
-  return launch_stream<OpTriSpace<3>>(img, out, nullptr, 0, coeffs, 9 * 35, B, H, W, flags, s, "trispace", ro, slab);
+  return dispatch_order(num_coeffs, [&](auto V, auto D) {
+    if constexpr (V == 5 && D == 4)
+      return launch_stream<OpTriSpaceRows>(img, out, nullptr, 0, coeffs, 9 * 126, B, H, W, flags, s, "trispace_rows", ro,
+                                           slab);
+    else if constexpr (D == 4)
+      return launch_stream<OpTriSpace<V>>(img, out, nullptr, 0, coeffs, 9 * 35, B, H, W, flags, s, "trispace", ro, slab);
+    else
+      return launch_stream<OpTriSpaceOrder<V, D>>(img, out, nullptr, 0, coeffs, 9 * PolyEval<V, D>::kCoeffs, B, H, W, flags, s,
+                                                  "trispace", ro, slab);
+  });
 }
 
 int curl_trispace_fwd_f32(const float* img, const float* coeffs, float* out, int B, int H, int W, int num_coeffs,
@@ -1036,14 +1074,21 @@ int curl_trispace_fwd_u8hwc(const uint8_t* img, const float* coeffs, const uint8
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (int rc = check_num_coeffs(num_coeffs, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)")) return rc;
+  int order;
+  if (int rc = unpack_num_coeffs(num_coeffs, num_coeffs, order)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (the byte output is an image)");
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (num_coeffs == 126)
-    return launch_stream_u8<OpTriSpaceRows>(img, out, nullptr, 0, white_mask, coeffs, 9 * 126, B, H, W, s,
-                                            "trispace_rows_u8hwc");
-  return launch_stream_u8<OpTriSpace<3>>(img, out, nullptr, 0, white_mask, coeffs, 9 * 35, B, H, W, s, "trispace_u8hwc");
+  return dispatch_order(num_coeffs, [&](auto V, auto D) {
+    if constexpr (V == 5 && D == 4)
+      return launch_stream_u8<OpTriSpaceRows>(img, out, nullptr, 0, white_mask, coeffs, 9 * 126, B, H, W, s,
+                                              "trispace_rows_u8hwc");
+    else if constexpr (D == 4)
+      return launch_stream_u8<OpTriSpace<V>>(img, out, nullptr, 0, white_mask, coeffs, 9 * 35, B, H, W, s, "trispace_u8hwc");
+    else
+      return launch_stream_u8<OpTriSpaceOrder<V, D>>(img, out, nullptr, 0, white_mask, coeffs, 9 * PolyEval<V, D>::kCoeffs, B, H,
+                                                     W, s, "trispace_u8hwc");
+  });
 }
 
 int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B, int H, int W, int num_variables,
@@ -1051,12 +1096,25 @@ int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (int rc = check_num_variables(num_variables)) return rc;
+  // the packed form of include/curl_hip_poly.h: the variable count in the low half, the polynomial degree in the high half
+  int degree = 4;
+  if (num_variables >> 16) {
+    degree = (num_variables >> 16) & 0xffff, num_variables &= 0xffff;
+    if ((num_variables != 5 && num_variables != 3) || degree > 4)
+      return fail(CURL_E_SHAPE, "num_variables with a polynomial degree in its high half: 5 or 3 variables, degree 1..4");
+  } else if (int rc = check_num_variables(num_variables)) {
+    return rc;
+  }
   const size_t HW = (size_t)H * W;
   const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, img, out));
   dispatch_vec_mask<kMasksNone>(p.aligned, CURL_MASK_NONE, [&](auto VEC, auto) {
-    if (num_variables == 5) hipLaunchKernelGGL((poly_layer_kernel<5, VEC>), p.grid, dim3(256), 0, (hipStream_t)stream, img, coeffs, out, p.n);
-    else hipLaunchKernelGGL((poly_layer_kernel<3, VEC>), p.grid, dim3(256), 0, (hipStream_t)stream, img, coeffs, out, p.n);
+    dispatch_order(poly_count(num_variables, degree), [&](auto V, auto D) {
+      void (*kernel)(const float*, const float*, float*, unsigned);
+      if constexpr (D == 4) kernel = poly_layer_kernel<V, VEC>;
+      else kernel = poly_layer_order_kernel<V, VEC, D>;
+      hipLaunchKernelGGL(kernel, p.grid, dim3(256), 0, (hipStream_t)stream, img, coeffs, out, p.n);
+      return 0;
+    });
   });
   return hip_done("poly_layer_kernel");
 }

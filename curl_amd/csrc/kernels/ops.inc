@@ -295,30 +295,33 @@ struct OpLayerTab : OpDefaults {
 // (kLdsFloats) and reach the packed FMAs as broadcast ds_read_b128 -> VGPR halves (op_sel).  Reading them
 // through a uniform global pointer instead made hipcc hoist all 1134 scalar loads and spill SGPRs into VGPR
 // lanes (3000 v_readlane/v_writelane per thread, 4.4 ms per batch).
-// Instantiated for V = 3 (the non-spatial model, 35 coefficients); the spatial V = 5 form runs as OpTriSpaceRows
-// below (this template with V = 5 is the earlier, 125-FMAs-per-output version of the same computation).
-template <int V>
-struct OpTriSpace : OpDefaults {
+// D = the polynomial order: OpTriSpace<V> is order 4, OpTriSpaceOrder<V, D> the orders below it.  Instantiated for V = 3 (the
+// non-spatial model) at every order and for V = 5 at orders 1-3; the spatial order-4 form runs as OpTriSpaceRows below
+// (OpTriSpace<5> is the earlier, 125-FMAs-per-output version of the same computation).  Orders 1-3 cost 55 / 20 / 5 FMAs per output with both coordinates
+// kept as variables: already fewer than the 69 the order-4 row fold leaves, on tiles that may cross rows and from a table
+// that needs a float's own alignment only (the row fold copies the raw table as 8-byte pairs: 9 x 21 floats is odd).
+template <int V, int D>
+struct OpTriSpaceOrder : OpDefaults {
   struct K {
     const float* coef;
-    unsigned W;
+    unsigned W, row0;  // row0: the slab's first row (the coordinates are the full image's)
     float fW, fH;
     bool residual_only;
   };
   static constexpr bool kMask = false;
   static constexpr int kUnroll = 1;
   static constexpr bool kSingleTileShape = true;
-  static constexpr int kLdsFloats = 9 * PolyEval<V>::kSeqStride;
+  static constexpr int kLdsFloats = 9 * PolyEval<V, D>::kSeqStride;
   static constexpr int kMinWavesPerSimd = kTriSpaceWaves;
   // LDS position p of polynomial q holds the coefficient the Horner scheme consumes p-th
   static __device__ __forceinline__ int stage_index(int i) {
-    constexpr int NC = PolyEval<V>::kCoeffs, NS = PolyEval<V>::kSeqStride;
+    constexpr int NC = PolyEval<V, D>::kCoeffs, NS = PolyEval<V, D>::kSeqStride;
     int q = i / NS, pos = i - q * NS;
-    return q * NC + PolyEval<V>::order(pos < NC ? pos : 0);  // padding slots are never read
+    return q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0);  // padding slots are never read
   }
   static constexpr bool kBlendMaskedOut = false;
   static __device__ __forceinline__ K load(const float* coef_img, const StreamArgs& a) {
-    return K{coef_img, a.W, (float)a.W, (float)a.H, a.op_flag != 0};
+    return K{coef_img, a.W, a.row0, (float)a.W, (float)a.H, a.op_flag != 0};
   }
   template <bool, int N>
   static __device__ __forceinline__ void apply_n(PxN<N>& p, const float (&)[N], const K& k, unsigned pix0) {
@@ -328,14 +331,17 @@ struct OpTriSpace : OpDefaults {
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         xw[i] = (float)col / k.fW;
-        yh[i] = (float)row / k.fH;
+        yh[i] = (float)(row + k.row0) / k.fH;
         if (++col == k.W) col = 0, ++row;
       }
     }
-    trispace_n<V, N, true>(p, xw, yh, k.coef, k.residual_only);
+    trispace_n<V, N, true, D>(p, xw, yh, k.coef, k.residual_only);
   }
   static __device__ __forceinline__ Px masked_out(const K&) { return Px{0.0f, 0.0f, 0.0f}; }
 };
+
+template <int V>
+struct OpTriSpace : OpTriSpaceOrder<V, 4> {};
 
 // The spatial polynomial path, one image row per block.  cat_coords' y = row/height is the same for every pixel
 // of a row, so the block folds y into the coefficients first (9 polynomials x 70 collapsed coefficients, <= 4
@@ -385,10 +391,10 @@ struct OpTriSpaceRows : OpDefaults {
 // The image's 3 x NC coefficients go to LDS in the order the Horner scheme consumes them (as OpTriSpace stages its nine
 // polynomials); a lane owns VEC pixels = VEC / 2 packed chains per coefficient read (VEC = 4: float4 loads per plane; 1: any
 // size or alignment, scalar chains).  n = HW / VEC.
-template <int V, int VEC>
-__global__ __launch_bounds__(256, 4) void poly_layer_kernel(const float* in, const float* coeffs, float* out, unsigned n) {
+template <int V, int VEC, int D>
+__device__ __forceinline__ void poly_layer_block(const float* in, const float* coeffs, float* out, unsigned n) {
   typedef typename Pack<VEC>::T T;
-  constexpr int NC = PolyEval<V>::kCoeffs, NS = PolyEval<V>::kSeqStride;
+  constexpr int NC = PolyEval<V, D>::kCoeffs, NS = PolyEval<V, D>::kSeqStride;
   __shared__ __attribute__((aligned(16))) float s_coef[3 * NS];
   const unsigned img = blockIdx.y;
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
@@ -400,7 +406,7 @@ __global__ __launch_bounds__(256, 4) void poly_layer_kernel(const float* in, con
   const float* table = coeffs + (size_t)img * 3 * NC;
   for (int j = threadIdx.x; j < 3 * NS; j += 256) {
     const int q = j / NS, pos = j - q * NS;
-    s_coef[j] = table[q * NC + PolyEval<V>::order(pos < NC ? pos : 0)];  // padding slots are never read
+    s_coef[j] = table[q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0)];  // padding slots are never read
   }
   __syncthreads();
   if (i >= n) return;
@@ -416,7 +422,7 @@ __global__ __launch_bounds__(256, 4) void poly_layer_kernel(const float* in, con
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     CURL_FENCE();
-    PolyEval<V>::template eval<float, true, VEC>(rs, vs, s_coef + c * NS);
+    PolyEval<V, D>::template eval<float, true, VEC>(rs, vs, s_coef + c * NS);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) o[c][e] = rs[e];
   }
@@ -428,4 +434,13 @@ __global__ __launch_bounds__(256, 4) void poly_layer_kernel(const float* in, con
     for (int e = 0; e < VEC; ++e) set_lane(y, e, o[c][e]);
     st<true>(q + (size_t)c * plane, y);
   }
+}
+// degree 4, and the degrees below it (ChannelPolyLayer(degree): model.py:206-216)
+template <int V, int VEC>
+__global__ __launch_bounds__(256, 4) void poly_layer_kernel(const float* in, const float* coeffs, float* out, unsigned n) {
+  poly_layer_block<V, VEC, 4>(in, coeffs, out, n);
+}
+template <int V, int VEC, int D>
+__global__ __launch_bounds__(256, 4) void poly_layer_order_kernel(const float* in, const float* coeffs, float* out, unsigned n) {
+  poly_layer_block<V, VEC, D>(in, coeffs, out, n);
 }

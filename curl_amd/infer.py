@@ -18,10 +18,10 @@ from . import ops
 from .convert_state import convert_state_dict
 
 
-def build_net(model_file, device, arch="curl"):
-    if arch == "trispace":  # infer.py:22-23
-        net = model_mod.TriSpaceRegNet(polynomial_order=4, spatial=True, is_train=False,
-                                       polylayer=model_mod.Deg4MobilePolyLayer())
+def build_net(model_file, device, arch="curl", polynomial_order=4):
+    if arch == "trispace":  # infer.py:22-23; a checkpoint trained at another order: ChannelPolyLayer of that order
+        net = model_mod.TriSpaceRegNet(polynomial_order=polynomial_order, spatial=True, is_train=False,
+                                       polylayer=model_mod.Deg4MobilePolyLayer() if polynomial_order == 4 else None)
     else:
         net = model_mod.GCURLNet(encoder_size=320)
     if model_file != "random":
@@ -75,10 +75,12 @@ def infer(argv=None):
     parser.add_argument("--arch", choices=("trispace", "curl"), default="trispace",
                         help="trispace = the reference's infer.py model (TriSpaceRegNet + Deg4MobilePolyLayer); "
                              "curl = the curve model (GCURLNet)")
+    parser.add_argument("--polynomial_order", type=int, default=4, choices=(1, 2, 3, 4),
+                        help="trispace: the polynomial_order the checkpoint was trained with (model.py:439)")
     args = parser.parse_args(argv)
     from PIL import Image
     device = torch.device("cuda:0")
-    net = build_net(args.model_file, device, args.arch)
+    net = build_net(args.model_file, device, args.arch, args.polynomial_order)
     img = np.asarray(Image.open(args.img_path))
     if img.ndim == 2:
         img = np.repeat(img[..., None], 3, axis=2)

@@ -365,7 +365,7 @@ def _poly_layer(img, coeffs):
 
 class ChannelPolyLayer(nn.Module):
     """model.py:206-333.  forward(img [B,V,H,W], coeffs [B,num_out,num_coeffs]) -> [B,num_out,H,W].
-    The HIP kernel covers what the fork uses: degree 4, V = 5 or 3, num_out = 3."""
+    The HIP kernels cover degree 1..4 (a kernel per degree), V = 5 or 3, num_out = 3."""
 
     def __init__(self, degree=3, num_variables=3, num_out=None):
         assert degree >= 0 and type(degree) == int, "`degree` must be non-negative integer"
@@ -386,9 +386,9 @@ class ChannelPolyLayer(nn.Module):
         assert img.shape[1] == self.num_variables, "There should be a polynomial variable per channel"
         assert len(coeffs.shape) == 3 and coeffs.shape[2] == self.num_coeffs, \
             f"coeffs must be [B, num_out, {self.num_coeffs}]"
-        if self.degree != 4 or self.num_variables not in (3, 5) or self.num_out != 3:
-            raise NotImplementedError("the HIP polynomial kernel is built for degree 4, 3 or 5 variables, 3 outputs "
-                                      "(the configurations model.py:426,450 use)")
+        if self.degree not in (1, 2, 3, 4) or self.num_variables not in (3, 5) or self.num_out != 3:
+            raise NotImplementedError("the HIP polynomial kernels are built for degree 1 to 4, 3 or 5 variables, 3 outputs "
+                                      f"(got degree {self.degree}, {self.num_variables} variables, {self.num_out} outputs)")
         return _poly_layer(img, coeffs)
 
 
@@ -405,7 +405,8 @@ class Deg4MobilePolyLayer(nn.Module):
 
 
 class PolyRegNet(nn.Module):
-    """model.py:418-436: encoder -> [B,3,35] coefficients -> sigmoid(ChannelPolyLayer(degree 4, 3 variables)(img)) * mask.
+    """model.py:418-436: encoder -> [B,3,n] coefficients -> sigmoid(ChannelPolyLayer(polynomial_order, 3 variables)(img)) * mask
+    (n = 35, 20, 10, 4 for orders 4..1).
     The polynomial layer is the HIP kernel (ops.poly_layer) and trains through its backward (ops.poly_layer_backward: the
     coefficient gradient only, the image is data); sigmoid and the mask product are stock torch.  The backbone is injectable
     as in TriSpaceRegNet (the reference downloads timm's efficientnetv2_rw_s)."""
@@ -428,7 +429,7 @@ class PolyRegNet(nn.Module):
 
 
 class TriSpaceRegNet(nn.Module):
-    """model.py:439-535: encoder -> [B,3,3,num_coeffs] -> per-pixel degree-4 polynomials in RGB, Lab and HSV.
+    """model.py:439-535: encoder -> [B,3,3,num_coeffs] -> per-pixel polynomials of order 1..4 in RGB, Lab and HSV.
     generate_residual + generate_image run as one fused kernel (ops.trispace_forward).
     The reference's backbone is timm `efficientnetv2_rw_t` (not installed here, needs a download); any module
     with a `.classifier` whose pooled feature width is `feature_width` can be injected."""
@@ -445,8 +446,10 @@ class TriSpaceRegNet(nn.Module):
         self.polylayer = polylayer if polylayer is not None else ChannelPolyLayer(
             degree=self.order, num_variables=self.num_in, num_out=self.num_channels)
         self.num_coeffs = self.polylayer.num_coeffs
-        if self.order != 4 or self.num_coeffs not in (126, 35):
-            raise NotImplementedError("fused kernel: polynomial_order 4 with spatial=True (126) or False (35)")
+        if self.order not in (1, 2, 3, 4) or self.num_coeffs not in ops.POLY_COEFFS[5] + ops.POLY_COEFFS[3]:
+            raise NotImplementedError("fused kernels: polynomial_order 1 to 4 with spatial=True (5 variables: 6, 21, 56, 126 "
+                                      f"coefficients) or False (3 variables: 4, 10, 20, 35); got order {self.order}, "
+                                      f"{self.num_coeffs} coefficients")
         if backbone is None:  # model.py:456: timm.create_model('efficientnetv2_rw_t')
             backbone = EfficientNetV2("efficientnetv2_rw_t") if feature_width == 1024 else \
                 CurveEncoder(num_outputs=1, num_features=feature_width, variant="efficientnetv2_rw_t")

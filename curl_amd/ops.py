@@ -167,11 +167,36 @@ def _layer_knots(L, R, H, B):
     return Lc, Rc, Hc, Kl, Kr, Kh, Lc.shape[1] + Rc.shape[1] + Hc.shape[1]
 
 
+# Coefficients per polynomial, C(V + d, d), by variable count V: orders d = 1..4.  The eight counts are all different, so a
+# table's width names its order and its variable count (include/curl_hip.h).
+POLY_COEFFS = {5: (6, 21, 56, 126), 3: (4, 10, 20, 35)}
+# ... and the order-4 width of the same variable count: the reference's monomial order is graded (model.py:222-246), so an
+# order-d table is the first n entries of the order-4 table of the same polynomial -- the backward kernels (order 4 only)
+# take it zero-padded and their coefficient gradient is cut back to n
+_ORDER4_WIDTH = {n: counts[3] for counts in POLY_COEFFS.values() for n in counts}
+
+
 def _check_coeffs(coeffs, B):
-    """The polynomial path's [B,3,3,126|35] coefficient table (then converted by _coeffs32)."""
+    """The polynomial path's [B,3,3,126|35] coefficient table, or a lower order's (then converted by _coeffs32)."""
     _need_device(coeffs, "coeffs")
-    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in (126, 35):
-        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)}")
+    if coeffs.dim() != 4 or coeffs.shape[:3] != (B, 3, 3) or coeffs.shape[3] not in _ORDER4_WIDTH:
+        raise ValueError(f"coeffs must be [B={B},3,3,126|35], got {tuple(coeffs.shape)} "
+                         "(orders 3, 2, 1: 56|20, 21|10, 6|4 in place of 126|35)")
+
+
+def _nc_arg(n):
+    """A table width as the forward entries' num_coeffs: 126 | 35 plain, a lower order's count with its order in the high half
+    (include/curl_hip_poly.h)."""
+    for counts in POLY_COEFFS.values():
+        if n in counts[:3]:
+            return _lib.poly_coeffs(n, counts.index(n) + 1)
+    return n
+
+
+def _pad_order4(c, width):
+    """An order-d coefficient table [..., n] as the order-4 table [..., width] of the same polynomials: zeros for the
+    monomials of degree > d.  A fresh allocation (8-byte aligned, as the 126-wide backward kernels want it)."""
+    return c if c.shape[-1] == width else torch.nn.functional.pad(c, (0, width - c.shape[-1]))
 
 
 def _mask(mask, img):
@@ -469,7 +494,7 @@ def trispace_forward_rows(img, coeffs, rows, out, residual_only=False):
     _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     out = _check_out(out, img)
-    rc = lib.curl_trispace_fwd_slab_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, r0, n, c.shape[3],
+    rc = lib.curl_trispace_fwd_slab_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, r0, n, _nc_arg(c.shape[3]),
                                         _lib.F_RESIDUAL_ONLY if residual_only else 0, _stream(img))
     _lib.check(rc, "curl_trispace_fwd_slab_f32")
     return out
@@ -729,14 +754,15 @@ class _ConvertFn(torch.autograd.Function):
 @_empty_ok()
 def trispace_forward(img, coeffs, residual_only=False, flags=0):
     """TriSpaceRegNet.generate_residual (+ generate_image unless residual_only), model.py:499-520, in one pass.
-    coeffs [B,3,3,NC] with NC = 126 (spatial) or 35; [:,0]=R, [:,1]=L, [:,2]=H (model.py:526)."""
+    coeffs [B,3,3,NC] with NC = 126 (spatial) or 35 for polynomial order 4, 56|20, 21|10, 6|4 for orders 3, 2, 1: each
+    order runs a kernel of its own; [:,0]=R, [:,1]=L, [:,2]=H (model.py:526)."""
     lib = _lib.load()
     img = _image(img)
     B, _, H, W = img.shape
     _check_coeffs(coeffs, B)
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     out = torch.empty_like(img)
-    rc = lib.curl_trispace_fwd_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, c.shape[3],
+    rc = lib.curl_trispace_fwd_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, _nc_arg(c.shape[3]),
                                    flags | (_lib.F_RESIDUAL_ONLY if residual_only else 0), _stream(img))
     _lib.check(rc, "curl_trispace_fwd_f32")
     return out
@@ -749,15 +775,16 @@ def trispace_backward(img, coeffs, grad_out, residual_only=False):
     img, grad_out = _image(img), _image(grad_out, "grad_out")
     B, _, H, W = img.shape
     _check_coeffs(coeffs, B)
-    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
-    nc = c.shape[3]
+    n = coeffs.shape[3]
+    nc = _ORDER4_WIDTH[n]  # orders 1-3 run the order-4 kernels on the zero-padded table (_pad_order4)
+    c = _pad_order4(_coeffs32(coeffs, pairs=n == 126), nc)
     g = torch.empty_like(c)
     nbytes = lib.curl_trispace_bwd_scratch_bytes(B, H, W, nc)
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=img.device)
     rc = lib.curl_trispace_bwd_f32(img.data_ptr(), c.data_ptr(), grad_out.data_ptr(), g.data_ptr(), scratch.data_ptr(),
                                    nbytes, B, H, W, nc, _lib.F_RESIDUAL_ONLY if residual_only else 0, _stream(img))
     _lib.check(rc, "curl_trispace_bwd_f32")
-    return g
+    return g if n == nc else g[..., :n].contiguous()
 
 
 TRISPACE_IMG_GRAD_TILE = 4096  # pixels per workgroup of trispace_backward_img's float4 kernel (256 lanes x 4 pixels x 4 steps)
@@ -774,7 +801,8 @@ def trispace_backward_img(img, coeffs, grad_out, residual_only=False):
     if grad_out.shape != img.shape:
         raise ValueError(f"grad_out must have img's shape {tuple(img.shape)}, got {tuple(grad_out.shape)}")
     _check_coeffs(coeffs, B)
-    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
+    n = coeffs.shape[3]
+    c = _pad_order4(_coeffs32(coeffs, pairs=n == 126), _ORDER4_WIDTH[n])  # orders 1-3: the order-4 kernel, as trispace_backward
     g = torch.empty_like(img)
     rc = lib.curl_trispace_bwd_img_f32(img.data_ptr(), c.data_ptr(), grad_out.data_ptr(), g.data_ptr(), B, H, W, c.shape[3],
                                        _lib.F_RESIDUAL_ONLY if residual_only else 0, _stream(img))
@@ -783,28 +811,31 @@ def trispace_backward_img(img, coeffs, grad_out, residual_only=False):
 
 
 def _poly_layer_args(img, coeffs):
-    """The stand-alone polynomial layer's tensor checks: img float32 [B,3|5,H,W], coeffs [B,3,35|126]."""
+    """The stand-alone polynomial layer's tensor checks: img float32 [B,3|5,H,W], coeffs [B,3,n] with n the coefficient count
+    of degree 1..4 in that many variables -> (img, coeffs, degree)."""
     _need_device(img, "img")
     _need_device(coeffs, "coeffs")
     if img.dim() != 4 or img.shape[1] not in (3, 5) or img.dtype != torch.float32:
         raise ValueError(f"img must be float32 [B,3|5,H,W], got {tuple(img.shape)} {img.dtype}")
     B, V, H, W = img.shape
-    nc = 126 if V == 5 else 35
-    if tuple(coeffs.shape) != (B, 3, nc):
-        raise ValueError(f"coeffs must be [B={B},3,{nc}], got {tuple(coeffs.shape)}")
-    return img.contiguous(), _coeffs32(coeffs, pairs=False)  # the poly_layer kernels read scalars
+    counts = POLY_COEFFS[V]
+    if coeffs.dim() != 3 or tuple(coeffs.shape[:2]) != (B, 3) or coeffs.shape[2] not in counts:
+        raise ValueError(f"coeffs must be [B={B},3,{counts[3]}], got {tuple(coeffs.shape)} "
+                         f"(degrees 3, 2, 1: {counts[2]}, {counts[1]}, {counts[0]} in place of {counts[3]})")
+    return img.contiguous(), _coeffs32(coeffs, pairs=False), counts.index(coeffs.shape[2]) + 1  # the kernels read scalars
 
 
 @_one_device
 def poly_layer(img, coeffs):
-    """ChannelPolyLayer(degree=4) / Deg4MobilePolyLayer forward (model.py:295-333, 399-415):
-    img [B,V,H,W] with V = 5 or 3, coeffs [B,3,126|35] -> [B,3,H,W]."""
+    """ChannelPolyLayer(degree) / Deg4MobilePolyLayer forward (model.py:295-333, 399-415):
+    img [B,V,H,W] with V = 5 or 3, coeffs [B,3,n] -> [B,3,H,W]; n = 126|35 for degree 4, 56|20, 21|10, 6|4 for degrees 3, 2, 1
+    (the width names the degree; each has a kernel of its own)."""
     lib = _lib.load()
-    img, c = _poly_layer_args(img, coeffs)
+    img, c, degree = _poly_layer_args(img, coeffs)
     B, V, H, W = img.shape
     out = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device)
-    _lib.check(lib.curl_poly_layer_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, V, _stream(img)),
-               "curl_poly_layer_f32")
+    _lib.check(lib.curl_poly_layer_f32(img.data_ptr(), c.data_ptr(), out.data_ptr(), B, H, W, _lib.poly_vars(V, degree),
+                                       _stream(img)), "curl_poly_layer_f32")
     return out
 
 
@@ -815,11 +846,14 @@ def poly_layer_bwd_tile(B, H, W):
 
 @_one_device
 def poly_layer_backward(img, coeffs, grad_out, need_img_grad=True, need_coeffs_grad=True):
-    """Backward of poly_layer: grad_out [B,3,H,W] = d loss / d out -> (grad_img [B,V,H,W] | None, grad_coeffs [B,3,35|126] |
-    None).  A gradient that is not needed is neither computed nor stored (its kernels are not launched)."""
+    """Backward of poly_layer: grad_out [B,3,H,W] = d loss / d out -> (grad_img [B,V,H,W] | None, grad_coeffs [B,3,n] |
+    None).  A gradient that is not needed is neither computed nor stored (its kernels are not launched).  Degrees 1-3 run the
+    degree-4 kernels on the zero-padded table (_pad_order4); their coefficient gradient is cut back to n."""
     lib = _lib.load()
-    img, c = _poly_layer_args(img, coeffs)
+    img, c, _ = _poly_layer_args(img, coeffs)
     B, V, H, W = img.shape
+    n = c.shape[2]
+    c = _pad_order4(c, POLY_COEFFS[V][3])
     _need_device(grad_out, "grad_out")
     if tuple(grad_out.shape) != (B, 3, H, W) or grad_out.dtype != torch.float32:
         raise ValueError(f"grad_out must be float32 [B={B},3,{H},{W}], got {tuple(grad_out.shape)} {grad_out.dtype}")
@@ -833,7 +867,7 @@ def poly_layer_backward(img, coeffs, grad_out, need_img_grad=True, need_coeffs_g
     rc = lib.curl_poly_layer_bwd_f32(img.data_ptr(), c.data_ptr(), grad_out.data_ptr(), _ptr(g_img), _ptr(g_c), _ptr(scratch),
                                      nbytes, B, H, W, V, 0, _stream(img))
     _lib.check(rc, "curl_poly_layer_bwd_f32")
-    return g_img, g_c
+    return g_img, (g_c if g_c is None or g_c.shape[2] == n else g_c[..., :n].contiguous())
 
 
 # ------------------------------------------------------------------ layout edges
@@ -929,7 +963,7 @@ def _trispace_forward_u8hwc_checked(img_u8, coeffs, white_mask=None):
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     wm = _white(white_mask, x)
     out = torch.empty_like(x)
-    rc = lib.curl_trispace_fwd_u8hwc(x.data_ptr(), c.data_ptr(), _ptr(wm), out.data_ptr(), B, H, W, c.shape[3], 0,
+    rc = lib.curl_trispace_fwd_u8hwc(x.data_ptr(), c.data_ptr(), _ptr(wm), out.data_ptr(), B, H, W, _nc_arg(c.shape[3]), 0,
                                      _stream(x))
     _lib.check(rc, "curl_trispace_fwd_u8hwc")
     return out

@@ -58,9 +58,9 @@ class SyntheticPairs(Dataset):
         return {"input_img": x, "output_img": y, "mask": mask, "name": f"synthetic_{i:05d}"}
 
 
-def build_net(arch, width, sync_bn, foreground_masks=False, paper_pwl=False):
+def build_net(arch, width, sync_bn, foreground_masks=False, paper_pwl=False, polynomial_order=4):
     if arch == "trispace":  # main.py:221
-        net = model.TriSpaceRegNet(polynomial_order=4, spatial=True, use_sync_bn=sync_bn,
+        net = model.TriSpaceRegNet(polynomial_order=polynomial_order, spatial=True, use_sync_bn=sync_bn,
                                    backbone=model.CurveEncoder(num_outputs=1, num_features=1024, width=width,
                                                                variant="efficientnetv2_rw_t"))  # model.py:456
     else:
@@ -91,6 +91,8 @@ def main(argv=None):
     ap.add_argument("--local_rank", type=int, default=0, help="accepted for torch.distributed.launch (main.py:91); "
                                                               "the LOCAL_RANK environment variable wins")
     ap.add_argument("--arch", choices=("trispace", "curl"), default="trispace")
+    ap.add_argument("--polynomial_order", type=int, default=4, choices=(1, 2, 3, 4),
+                    help="trispace: TriSpaceRegNet(polynomial_order=...) (model.py:439); each order runs a kernel of its own")
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI; gloo for rehearsals")
     ap.add_argument("--crop", type=int, default=256, help="data.py:86 crops 256x256 .. 'resize to 320' variants")
     ap.add_argument("--train_items", type=int, default=256)
@@ -141,7 +143,8 @@ def main(argv=None):
         dd = data.filter_data_dict(data.get_data_dict(root), data.get_data_ids(os.path.join(root, "images_inference.txt")))
         loader = DataLoader(data.Dataset(dd, normaliser=1, is_train=False, crop_h=args.crop, crop_w=args.crop),
                             batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers)
-        net = build_net(args.arch, args.width, sync_bn=False, foreground_masks=args.foreground_masks, paper_pwl=args.paper_pwl)
+        net = build_net(args.arch, args.width, sync_bn=False, foreground_masks=args.foreground_masks, paper_pwl=args.paper_pwl,
+                        polynomial_order=args.polynomial_order)
         ckpt = torch.load(args.checkpoint_filepath, map_location="cpu")
         net.load_state_dict(convert_state_dict(ckpt["model_state_dict"]))  # DP/DDP "module." prefixes removed
         net = net.to(device).eval()
@@ -173,7 +176,7 @@ def main(argv=None):
                               num_workers=args.num_workers, sampler=valid_sampler)
 
     net = build_net(args.arch, args.width, sync_bn=ddp and args.backend == "nccl", foreground_masks=args.foreground_masks,
-                    paper_pwl=args.paper_pwl).to(device)
+                    paper_pwl=args.paper_pwl, polynomial_order=args.polynomial_order).to(device)
     if args.channels_last:
         net = net.to(memory_format=torch.channels_last)
     autocast = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if args.amp == "bf16" else contextlib.nullcontext

@@ -284,9 +284,14 @@ int curl_hsv_stage_bwd_f32(const float* img, const void* mask, int mask_kind, co
  *           fork's live model (infer.py:44-45, main.py:283) -- with polylayer = Deg4MobilePolyLayer
  *           (model.py:336-415) or ChannelPolyLayer(degree=4) (model.py:206-333), as ONE pass over the pixels.
  * coeffs [B,3,3,num_coeffs] = the reshaped head output (model.py:523-526; [:,0]=R, [:,1]=L, [:,2]=H).
- * num_coeffs 126 = spatial model (5 variables: colour + x/W + y/H), 35 = non-spatial (3 variables).
- * coeffs must be 8-byte aligned (CURL_E_SHAPE otherwise; true of any allocation's start): the kernels copy an image's
- * table into LDS as 8-byte pairs.  The same holds for the u8 and backward entry points below.
+ * num_coeffs 126 = spatial model (5 variables: colour + x/W + y/H), 35 = non-spatial (3 variables): polynomial order 4.
+ * Orders 1..3 (polynomial_order of the reference's TriSpaceRegNet, model.py:439-454) have 6, 21, 56 | 4, 10, 20
+ * coefficients; their count travels with the order in its high 16 bits, as the last curve's knot count does in a knot
+ * argument -- curl_hip_poly.h has the macro and the rules.  Each order runs a kernel built for it.  A plain count other than
+ * 126 | 35, or a count that is not its order's, is CURL_E_KNOTS.  The same holds for the slab and u8 entry points below.
+ * Alignment of coeffs (CURL_E_SHAPE otherwise):  126: 8-byte aligned (true of any allocation's start) -- the kernel copies
+ * an image's table into LDS as 8-byte pairs, and so do the backward entry points;  56, 35, 21, 20, 10, 6, 4: 4-byte
+ * aligned, a float's own alignment -- their kernels read the table as scalars.
  * Default output: clamp(img + residual, 0, 1); with CURL_F_RESIDUAL_ONLY the residual itself. */
 int curl_trispace_fwd_f32(const float* img, const float* coeffs, float* out, int B, int H, int W,
                           int num_coeffs, unsigned flags, curl_stream_t stream);
@@ -317,14 +322,22 @@ int curl_layer_fwd_u8hwc(const uint8_t* img, const void* mask, int mask_kind, co
  *           TriSpaceRegNet.generate_residual, main.py:287) -- the image is data, its gradient is not produced.
  * grad_out [B,3,H,W] -> grad_coeffs [B,3,3,num_coeffs] (ASSIGNED).  flags: CURL_F_RESIDUAL_ONLY as in the forward.
  * Three passes: per-pixel upstream gradients, register-tiled outer products with the monomials, fixed-order
- * float64 reduction (no atomics).  scratch: curl_trispace_bwd_scratch_bytes (72 B per pixel + tile partials). */
+ * float64 reduction (no atomics).  scratch: curl_trispace_bwd_scratch_bytes (72 B per pixel + tile partials).
+ * num_coeffs 126 or 35 here (and in curl_trispace_bwd_img_f32 and curl_poly_layer_bwd_f32): order 4 only.  The reference's
+ * monomial order is graded, so an order-d table is the first n entries of the order-4 table of the same polynomial: pad each
+ * [.., n] row with zeros to 126 | 35, call the order-4 entry, and take the first n entries of each grad_coeffs row (the
+ * image gradient needs no change).  curl_amd.ops does exactly this. */
 size_t curl_trispace_bwd_scratch_bytes(int B, int H, int W, int num_coeffs);
 int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* grad_out, float* grad_coeffs,
                           void* scratch, size_t scratch_bytes, int B, int H, int W, int num_coeffs,
                           unsigned flags, curl_stream_t stream);
 
-/* replaces: ChannelPolyLayer(degree=4).forward / Deg4MobilePolyLayer.forward  model.py:295-333, 399-415
- * img [B,num_variables,H,W] (num_variables 5 or 3), coeffs [B,3,num_coeffs] -> out [B,3,H,W]. */
+/* replaces: ChannelPolyLayer(degree).forward / Deg4MobilePolyLayer.forward  model.py:295-333, 399-415
+ * img [B,V,H,W] (V = 5 or 3), coeffs [B,3,num_coeffs] -> out [B,3,H,W].
+ * num_variables = V for the degree-4 layer (num_coeffs 126 | 35).  Degrees 1..3 (num_coeffs = C(V + degree, degree) = 6, 21,
+ * 56 for V = 5, 4, 10, 20 for V = 3) travel in the high 16 bits of num_variables, as the last curve's knot count does in a
+ * knot argument: curl_hip_poly.h has the macro that packs them and the rules.  A high half of 0 is degree 4, so a plain 5 or
+ * 3 keeps its meaning.  coeffs: a float's own alignment for every degree (read as scalars). */
 int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B, int H, int W,
                         int num_variables, curl_stream_t stream);
 

@@ -324,6 +324,11 @@ def main():
     for nvars in (5, 3):
         parts.append(gen(3, nvars)[1])
         parts.append(gen_deriv(4, nvars))
+    # polynomial orders 1 and 2 of the forward kernels (order 3 is the scheme above, order 4 the first block): the per-pixel
+    # form in 5 and 3 variables -- the lower orders do not take the per-row y-collapse
+    for degree in (2, 1):
+        for nvars in (5, 3):
+            parts.append(gen(degree, nvars)[1])
     open(out, "w").write("\n".join(parts))
     print("wrote", out)
 
