@@ -61,7 +61,7 @@ def build_fastcall(force=False):
     import sysconfig
     import torch
     out = fastcall_path()
-    deps = [FAST_SRC, INCLUDE, os.path.abspath(__file__)]
+    deps = [FAST_SRC, os.path.join(HERE, "csrc", "poly_pairs.h"), INCLUDE, os.path.abspath(__file__)]
     if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps):
         return out
     tdir = os.path.dirname(torch.__file__)

@@ -13,6 +13,7 @@
 #pragma once
 constexpr int kPolySel = 0;  // the converters' threshold selects inside the polynomial model: 0 eager; 2 (predicated) spills 688 B per lane at the kernel's 128-VGPR budget, 1 (skipped per wave too) 1.1 KB -- round 3
 #include "curl_math_bwd.h"
+#include "poly_pairs.h"
 
 namespace curlm {
 
@@ -102,58 +103,46 @@ struct PolyCoef<curl_f2> {
 // gradients come from the order-4 kernels on the zero-padded table (include/curl_hip.h).
 template <int V, int D = 4>
 struct PolyEval;
-template <>
-struct PolyEval<5, 4> {
-  static constexpr int kCoeffs = 126;
-  static constexpr int kSeqStride = 128;  // floats per polynomial in the consumption-order (LDS) layout: 16-byte multiple
-  template <class F, bool SEQ, int NP>
-  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][5], const float* c) { poly_d4_v5<F, SEQ, NP>(out, v, c); }
-  static CURL_HD int order(int pos) { return kPolyOrder_d4_v5[pos]; }
-  static constexpr int kChunk = 42, kChunks = 3;
-  template <int C>
-  static CURL_HD void monomials(float (&m)[42], const float (&pw)[5][5]) { mono_d4_v5<C>(m, pw); }
-};
-template <>
-struct PolyEval<4, 4> {  // 3 colour channels + x/W: the per-row collapsed form of the 5-variable polynomial (below)
-  static constexpr int kCoeffs = 70;
-  static constexpr int kSeqStride = 72;
-  template <class F, bool SEQ, int NP>
-  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][4], const float* c) { poly_d4_v4<F, SEQ, NP>(out, v, c); }
-  static CURL_HD int order(int pos) { return kPolyOrder_d4_v4[pos]; }
-  static constexpr int kChunk = 35, kChunks = 2;  // the x-folded coefficient gradient (coef_grad_accumulate_foldx)
-  template <int C>
-  static CURL_HD void monomials(float (&m)[35], const float (&pw)[4][5]) { mono_d4_v4<C>(m, pw); }
-};
-template <>
-struct PolyEval<3, 4> {
-  static constexpr int kCoeffs = 35;
-  static constexpr int kSeqStride = 36;
-  template <class F, bool SEQ, int NP>
-  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][3], const float* c) { poly_d4_v3<F, SEQ, NP>(out, v, c); }
-  static CURL_HD int order(int pos) { return kPolyOrder_d4_v3[pos]; }
-  static constexpr int kChunk = 35, kChunks = 1;
-  template <int C>
-  static CURL_HD void monomials(float (&m)[35], const float (&pw)[3][5]) { mono_d4_v3<C>(m, pw); }
-};
-
-// orders 1-3: kCoeffs = C(V + D, D); kSeqStride = kCoeffs rounded up to a 16-byte multiple (PolyCoef<curl_f2>::pair reads the
-// aligned group of four around a coefficient)
-#define POLY_LOW_ORDER(V, D, NCOEF)                                                                                 \
-  template <>                                                                                                       \
-  struct PolyEval<V, D> {                                                                                           \
-    static constexpr int kCoeffs = NCOEF;                                                                           \
-    static constexpr int kSeqStride = (NCOEF + 3) & ~3;                                                             \
-    template <class F, bool SEQ, int NP>                                                                            \
+// kCoeffs = C(V + D, D) (poly_count, poly_pairs.h): the extent of the generated consumption-order table.  kSeqStride = floats per polynomial in the
+// consumption-order (LDS) layout, kCoeffs rounded up to a 16-byte multiple (PolyCoef<curl_f2>::pair reads the aligned group of
+// four around a coefficient).  The trailing arguments are members of that scheme alone.
+#define POLY_EVAL(V, D, ...)                                                                                                 \
+  template <>                                                                                                                \
+  struct PolyEval<V, D> {                                                                                                    \
+    static constexpr int kCoeffs = sizeof(kPolyOrder_d##D##_v##V) / sizeof(kPolyOrder_d##D##_v##V[0]);                       \
+    static_assert(kCoeffs == poly_count(V, D), "one coefficient per monomial of total degree <= D");                         \
+    static constexpr int kSeqStride = (kCoeffs + 3) & ~3;                                                                    \
+    template <class F, bool SEQ, int NP>                                                                                     \
     static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][V], const float* c) { poly_d##D##_v##V<F, SEQ, NP>(out, v, c); } \
-    static CURL_HD int order(int pos) { return kPolyOrder_d##D##_v##V[pos]; }                                       \
+    static CURL_HD int order(int pos) { return kPolyOrder_d##D##_v##V[pos]; }                                                \
+    __VA_ARGS__                                                                                                              \
   };
-POLY_LOW_ORDER(5, 3, 56)
-POLY_LOW_ORDER(5, 2, 21)
-POLY_LOW_ORDER(5, 1, 6)
-POLY_LOW_ORDER(3, 3, 20)
-POLY_LOW_ORDER(3, 2, 10)
-POLY_LOW_ORDER(3, 1, 4)
-#undef POLY_LOW_ORDER
+// order 4 only: the monomials in CHUNKS chunks of CHUNK, for the coefficient gradients
+#define POLY_MONOMIALS(V, CHUNK, CHUNKS)               \
+  static constexpr int kChunk = CHUNK, kChunks = CHUNKS; \
+  template <int C>                                     \
+  static CURL_HD void monomials(float (&m)[CHUNK], const float (&pw)[V][5]) { mono_d4_v##V<C>(m, pw); }
+POLY_EVAL(5, 4, POLY_MONOMIALS(5, 42, 3))
+POLY_EVAL(4, 4, POLY_MONOMIALS(4, 35, 2))  // 3 colour channels + x/W: the per-row collapsed form of the 5-variable polynomial (below); the x-folded coefficient gradient (coef_grad_accumulate_foldx)
+POLY_EVAL(3, 4, POLY_MONOMIALS(3, 35, 1))
+POLY_EVAL(5, 3, )
+POLY_EVAL(5, 2, )
+POLY_EVAL(5, 1, )
+POLY_EVAL(3, 3, )
+POLY_EVAL(3, 2, )
+POLY_EVAL(3, 1, )
+#undef POLY_MONOMIALS
+#undef POLY_EVAL
+
+// Slot `slot` of a staged table [n][kSeqStride] (the LDS copy of n polynomials, each in the order its Horner scheme consumes
+// it) -> the index into the reference-order table [n][kCoeffs] of the coefficient that belongs there.  Padding slots are never
+// read: they name the coefficient the scheme consumes first, a valid index.
+template <int V, int D = 4>
+CURL_HD int poly_seq_index(int slot) {
+  constexpr int NC = PolyEval<V, D>::kCoeffs, NS = PolyEval<V, D>::kSeqStride;
+  const int q = slot / NS, pos = slot - q * NS;
+  return q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0);
+}
 
 // out[o][i] = P_o(vars[.][i]) for the N pixels of a lane; coef = [3][NC] of one image and one space, in the
 // reference's order (SEQ = false) or permuted into Horner consumption order (SEQ = true).  vars is plane-major.
@@ -526,26 +515,20 @@ CURL_HD void coef_grad_expand_foldx(float (&e)[PolyFoldX<C>::kSlice], const fold
 // or 56 (V = 5) coefficients per image, formed once per workgroup and evaluated with the degree-3 Horner scheme -- 19 / 55
 // FMAs each, the lane's pixels in lock step as in the forward.  (Against the monomial form sum_u D[u] * m_u: the same FMA
 // count within 2 %, no 56 live monomials per pixel.)
+// The derivative polynomials are evaluated by the degree-3 scheme: eval, order and the term count are PolyEval<V, 3>'s.
 template <int V>
 struct PolyDeriv;
-template <>
-struct PolyDeriv<5> {
-  static constexpr int kTerms = 56;
-  template <class F, bool SEQ, int NP>
-  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][5], const float* c) { poly_d3_v5<F, SEQ, NP>(out, v, c); }
-  static CURL_HD int order(int pos) { return kPolyOrder_d3_v5[pos]; }
-  static CURL_HD int src(int i, int u) { return kPolyDerivIdx_d4_v5[i][u]; }
-  static CURL_HD float mul(int i, int u) { return (float)kPolyDerivMul_d4_v5[i][u]; }
-};
-template <>
-struct PolyDeriv<3> {
-  static constexpr int kTerms = 20;
-  template <class F, bool SEQ, int NP>
-  static CURL_HD void eval(F (&out)[NP], const F (&v)[NP][3], const float* c) { poly_d3_v3<F, SEQ, NP>(out, v, c); }
-  static CURL_HD int order(int pos) { return kPolyOrder_d3_v3[pos]; }
-  static CURL_HD int src(int i, int u) { return kPolyDerivIdx_d4_v3[i][u]; }
-  static CURL_HD float mul(int i, int u) { return (float)kPolyDerivMul_d4_v3[i][u]; }
-};
+#define POLY_DERIV(V)                                                                                  \
+  template <>                                                                                          \
+  struct PolyDeriv<V> : PolyEval<V, 3> {                                                               \
+    static constexpr int kTerms = kCoeffs;                                                             \
+    static_assert(kTerms == kSeqStride, "a 16-byte multiple: the staged polynomials need no padding"); \
+    static CURL_HD int src(int i, int u) { return kPolyDerivIdx_d4_v##V[i][u]; }                       \
+    static CURL_HD float mul(int i, int u) { return (float)kPolyDerivMul_d4_v##V[i][u]; }              \
+  };
+POLY_DERIV(5)
+POLY_DERIV(3)
+#undef POLY_DERIV
 // Entry j of an image's derivative table [V][3][kTerms], polynomial (i, o) in the order the degree-3 scheme consumes its
 // coefficients.  coef = [3][NC] of the image, reference order.  (kTerms is a multiple of 4: every polynomial starts on a
 // 16-byte boundary of the LDS copy.)
@@ -593,9 +576,9 @@ struct TriImgGrad {
 template <int V>
 CURL_HD float trispace_img_grad_stage(const float* coef, int j) {
   constexpr int NC = PolyEval<V>::kCoeffs, NS = PolyEval<V>::kSeqStride;
-  if (j < TriImgGrad<V>::kFwd) {
+  if (j < TriImgGrad<V>::kFwd) {  // poly_seq_index's rule, with zeros in the padding slots (never read either)
     const int q = j / NS, pos = j - q * NS;
-    return pos < NC ? coef[q * NC + PolyEval<V>::order(pos)] : 0.0f;  // (padding slots are never read)
+    return pos < NC ? coef[q * NC + PolyEval<V>::order(pos)] : 0.0f;
   }
   j -= TriImgGrad<V>::kFwd;
   const int s = j / TriImgGrad<V>::kDerSpace;

@@ -19,6 +19,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include "../../include/curl_hip.h"
+#include "poly_pairs.h"
 
 namespace {
 
@@ -156,7 +157,7 @@ py::object trispace_fwd_u8hwc(const at::Tensor& img, const at::Tensor& coeffs, c
   if (B > INT_MAX || H > INT_MAX || W > INT_MAX) return py::none();
   // (tables of polynomial orders 1-3 -- any width but 126 | 35 -- go to the checked ctypes path, which packs their order)
   if (!plain(coeffs, at::kFloat, dev) || coeffs.dim() != 4 || coeffs.size(0) != B || coeffs.size(1) != 3 || coeffs.size(2) != 3 ||
-      (coeffs.size(3) != 126 && coeffs.size(3) != 35) || (reinterpret_cast<uintptr_t>(coeffs.data_ptr()) & 7u))
+      coeffs.size(3) > INT_MAX || !is_poly_count((int)coeffs.size(3), 4) || (reinterpret_cast<uintptr_t>(coeffs.data_ptr()) & 7u))
     return py::none();
   const uint8_t* wm = nullptr;
   if (white_mask.has_value() && white_mask->defined()) {

@@ -13,7 +13,7 @@ static int check_img(const void* in, const void* out, int B, int H, int W) {
 // every image's table starts on an 8-byte boundary when the first one does).  Every other width (35, and orders 1-3: 4, 10,
 // 20, 6, 21, 56) is read as scalars: a float's own 4-byte alignment is all they need.
 static int check_coeffs_aligned(const float* coeffs, int num_coeffs) {
-  if (num_coeffs == 126 && (uintptr_t)coeffs % 8) return fail(CURL_E_SHAPE, "coeffs must be 8-byte aligned (num_coeffs = 126)");
+  if (num_coeffs == PolyEval<5>::kCoeffs && (uintptr_t)coeffs % 8) return fail(CURL_E_SHAPE, "coeffs must be 8-byte aligned (num_coeffs = 126)");
   if ((uintptr_t)coeffs % 4) return fail(CURL_E_SHAPE, "coeffs must be 4-byte aligned");
   return 0;
 }
@@ -415,39 +415,56 @@ static int check_scratch(const void* scratch, size_t bytes, size_t need, bool wa
   if (!scratch || (wants_16_byte_alignment && !on_grid(16, scratch)) || bytes < need) return fail(CURL_E_WORKSPACE, msg);
   return 0;
 }
-static int check_num_coeffs(int num_coeffs, const char* msg) { return (num_coeffs != 126 && num_coeffs != 35) ? fail(CURL_E_KNOTS, msg) : 0; }
+// The counts, the (variables, order) pairs and which of them is which come from kPolyPairs (poly_pairs.h) everywhere below.
+static int check_num_coeffs(int num_coeffs, const char* msg) { return is_poly_count(num_coeffs, 4) ? 0 : fail(CURL_E_KNOTS, msg); }
 static int check_num_variables(int num_variables) {
-  return (num_variables != 5 && num_variables != 3) ? fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)") : 0;
+  return is_poly_pair(num_variables, 4) ? 0 : fail(CURL_E_SHAPE, "num_variables must be 5 or 3 (degree 4)");
 }
 // The polynomial order of a forward call.  The eight coefficient counts C(V + D, D), V = 3 | 5, D = 1..4, are all different, so
 // a count names its order and its variable count; the entries still want the order said (curl_hip_poly.h packs it into the
 // high half of num_coeffs, as CURL_K_UNEVEN packs a knot count) because a plain count other than 126 | 35 has always been
 // CURL_E_KNOTS.  A high half of 0 is order 4.  -> the count, checked against the order; 0 after fail().
-static int poly_count(int V, int D) { return V == 5 ? (D == 4 ? 126 : D == 3 ? 56 : D == 2 ? 21 : 6) : (D == 4 ? 35 : D == 3 ? 20 : D == 2 ? 10 : 4); }
 static int unpack_num_coeffs(int packed, int& count, int& order) {
   count = packed & 0xffff, order = (packed >> 16) & 0xffff;
   if (order == 0) {
     order = 4;
     return check_num_coeffs(packed, "num_coeffs must be 126 (degree 4, 5 variables) or 35 (degree 4, 3 variables)");
   }
-  if (order > 4 || (count != poly_count(5, order) && count != poly_count(3, order)))
+  if (!is_poly_count(count, order))
     return fail(CURL_E_KNOTS, "num_coeffs with a polynomial order in its high half: the order must be 1..4 and the count 6 | 21 | 56 | 126 (5 variables) or 4 | 10 | 20 | 35 (3 variables) for orders 1..4");
   return 0;
 }
-// f(V, D) with both as compile-time constants, for a count unpack_num_coeffs accepted
+// The same for curl_poly_layer_f32's num_variables: the variable count in the low half, the degree in the high half.
+static int unpack_num_variables(int packed, int& V, int& degree) {
+  V = packed & 0xffff, degree = (packed >> 16) & 0xffff;
+  if (degree == 0) {
+    degree = 4;
+    return check_num_variables(packed);
+  }
+  if (!is_poly_pair(V, degree))
+    return fail(CURL_E_SHAPE, "num_variables with a polynomial degree in its high half: 5 or 3 variables, degree 1..4");
+  return 0;
+}
+// f(V, D) with both as compile-time constants, for a count unpack_num_coeffs accepted (-1: no pair has that count)
+template <class F, size_t... I>
+static int dispatch_order(int count, F&& f, std::index_sequence<I...>) {
+  int rc = -1;
+  (void)((count == poly_count(kPolyPairs[I].V, kPolyPairs[I].D) && (rc = f(int_c<kPolyPairs[I].V>(), int_c<kPolyPairs[I].D>()), true)) || ...);
+  return rc;
+}
 template <class F>
 static int dispatch_order(int count, F&& f) {
-  switch (count) {
-    case 126: return f(int_c<5>(), int_c<4>());
-    case 56: return f(int_c<5>(), int_c<3>());
-    case 21: return f(int_c<5>(), int_c<2>());
-    case 6: return f(int_c<5>(), int_c<1>());
-    case 35: return f(int_c<3>(), int_c<4>());
-    case 20: return f(int_c<3>(), int_c<3>());
-    case 10: return f(int_c<3>(), int_c<2>());
-    default: return f(int_c<3>(), int_c<1>());
-  }
+  return dispatch_order(count, f, std::make_index_sequence<sizeof(kPolyPairs) / sizeof(kPolyPairs[0])>());
 }
+// The forward kernel of a pair: the row fold for the spatial order 4, OpTriSpace<V> at order 4, the order's own op below it;
+// `where` names it in curl_last_error
+template <int V, int D>
+struct TriSpaceOp {
+  static constexpr bool kRows = V == 5 && D == 4;
+  typedef std::conditional_t<kRows, OpTriSpaceRows, std::conditional_t<D == 4, OpTriSpace<V>, OpTriSpaceOrder<V, D>>> Op;
+  static constexpr unsigned kCoefStride = 9 * PolyEval<V, D>::kCoeffs;  // floats per image
+  static constexpr const char* where(bool u8) { return kRows ? (u8 ? "trispace_rows_u8hwc" : "trispace_rows") : (u8 ? "trispace_u8hwc" : "trispace"); }
+};
 
 // chain_kernel's launch in two steps, so that a caller's own launches (the knot prep, apply_curve's regulariser) come after
 // every check: the plan (verdict, tuning fields, groups per lane and LDS reservation, grid), then the launch
@@ -537,7 +554,7 @@ static StripGeo strip_geo(int B, int H, int W) {
 
 // the tiles of the tri-space backward's accumulation pass (one row of partials each)
 static size_t tri_bwd_tiles(int B, int H, int W, int num_coeffs) {
-  return (num_coeffs == 126 && kTriBwdStrips) ? strip_geo(B, H, W).tiles() : tri_tiles(B, (size_t)H * W);
+  return (num_coeffs == PolyEval<5>::kCoeffs && kTriBwdStrips) ? strip_geo(B, H, W).tiles() : tri_tiles(B, (size_t)H * W);
 }
 
 template <int V>
@@ -1044,14 +1061,8 @@ static int trispace_fwd_impl(const float* img, const float* coeffs, float* out, 
   int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
   return dispatch_order(num_coeffs, [&](auto V, auto D) {
-    if constexpr (V == 5 && D == 4)
-      return launch_stream<OpTriSpaceRows>(img, out, nullptr, 0, coeffs, 9 * 126, B, H, W, flags, s, "trispace_rows", ro,
-                                           slab);
-    else if constexpr (D == 4)
-      return launch_stream<OpTriSpace<V>>(img, out, nullptr, 0, coeffs, 9 * 35, B, H, W, flags, s, "trispace", ro, slab);
-    else
-      return launch_stream<OpTriSpaceOrder<V, D>>(img, out, nullptr, 0, coeffs, 9 * PolyEval<V, D>::kCoeffs, B, H, W, flags, s,
-                                                  "trispace", ro, slab);
+    typedef TriSpaceOp<V, D> T;
+    return launch_stream<typename T::Op>(img, out, nullptr, 0, coeffs, T::kCoefStride, B, H, W, flags, s, T::where(false), ro, slab);
   });
 }
 
@@ -1080,14 +1091,8 @@ int curl_trispace_fwd_u8hwc(const uint8_t* img, const float* coeffs, const uint8
   if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
   hipStream_t s = (hipStream_t)stream;
   return dispatch_order(num_coeffs, [&](auto V, auto D) {
-    if constexpr (V == 5 && D == 4)
-      return launch_stream_u8<OpTriSpaceRows>(img, out, nullptr, 0, white_mask, coeffs, 9 * 126, B, H, W, s,
-                                              "trispace_rows_u8hwc");
-    else if constexpr (D == 4)
-      return launch_stream_u8<OpTriSpace<V>>(img, out, nullptr, 0, white_mask, coeffs, 9 * 35, B, H, W, s, "trispace_u8hwc");
-    else
-      return launch_stream_u8<OpTriSpaceOrder<V, D>>(img, out, nullptr, 0, white_mask, coeffs, 9 * PolyEval<V, D>::kCoeffs, B, H,
-                                                     W, s, "trispace_u8hwc");
+    typedef TriSpaceOp<V, D> T;
+    return launch_stream_u8<typename T::Op>(img, out, nullptr, 0, white_mask, coeffs, T::kCoefStride, B, H, W, s, T::where(true));
   });
 }
 
@@ -1096,15 +1101,8 @@ int curl_poly_layer_f32(const float* img, const float* coeffs, float* out, int B
   g_err[0] = 0;
   if (int rc = check_img(img, out, B, H, W)) return rc;
   if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  // the packed form of include/curl_hip_poly.h: the variable count in the low half, the polynomial degree in the high half
-  int degree = 4;
-  if (num_variables >> 16) {
-    degree = (num_variables >> 16) & 0xffff, num_variables &= 0xffff;
-    if ((num_variables != 5 && num_variables != 3) || degree > 4)
-      return fail(CURL_E_SHAPE, "num_variables with a polynomial degree in its high half: 5 or 3 variables, degree 1..4");
-  } else if (int rc = check_num_variables(num_variables)) {
-    return rc;
-  }
+  int degree;  // (the packed form of include/curl_hip_poly.h)
+  if (int rc = unpack_num_variables(num_variables, num_variables, degree)) return rc;
   const size_t HW = (size_t)H * W;
   const Pointwise p = pointwise(HW, B, planes_vec4(HW, nullptr, CURL_MASK_NONE, 16, img, out));
   dispatch_vec_mask<kMasksNone>(p.aligned, CURL_MASK_NONE, [&](auto VEC, auto) {
@@ -1369,7 +1367,7 @@ int curl_loss_terms_bwd_f32(const float* pred, const float* target, const void* 
 }
 
 size_t curl_trispace_bwd_scratch_bytes(int B, int H, int W, int num_coeffs) {
-  if (B <= 0 || H <= 0 || W <= 0 || (num_coeffs != 126 && num_coeffs != 35)) return 0;
+  if (B <= 0 || H <= 0 || W <= 0 || !is_poly_count(num_coeffs, 4)) return 0;
   size_t HW = (size_t)H * W;
   return ((size_t)B * 18 * HW + (size_t)B * tri_bwd_tiles(B, H, W, num_coeffs) * 9 * num_coeffs) * sizeof(float);
 }
@@ -1392,15 +1390,15 @@ int curl_trispace_bwd_f32(const float* img, const float* coeffs, const float* gr
   float* pxbuf = (float*)scratch;
   float* partial = pxbuf + (size_t)B * 18 * HW;
   int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
-  if (num_coeffs == 126) launch_trispace_bwd<5>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
+  if (num_coeffs == PolyEval<5>::kCoeffs) launch_trispace_bwd<5>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
   else launch_trispace_bwd<3>(img, coeffs, grad_out, grad_coeffs, pxbuf, partial, B, H, W, ro, (hipStream_t)stream);
   return hip_done("trispace backward kernels");
 }
 
 size_t curl_poly_layer_bwd_scratch_bytes(int B, int H, int W, int num_variables) {
-  if (B <= 0 || H <= 0 || W <= 0 || (num_variables != 5 && num_variables != 3)) return 0;
+  if (B <= 0 || H <= 0 || W <= 0 || !is_poly_pair(num_variables, 4)) return 0;
   const size_t HW = (size_t)H * W;
-  return (size_t)B * poly_bwd_tiles(B, HW) * 3 * (num_variables == 5 ? 126 : 35) * sizeof(float);
+  return (size_t)B * poly_bwd_tiles(B, HW) * 3 * poly_count(num_variables, 4) * sizeof(float);
 }
 
 int curl_poly_layer_bwd_f32(const float* img, const float* coeffs, const float* grad_out, float* grad_img, float* grad_coeffs,

@@ -29,7 +29,7 @@ int curl_trispace_bwd_img_f32(const float* img, const float* coeffs, const float
   if ((const void*)grad_img == (const void*)img || (const void*)grad_img == (const void*)coeffs)
     return fail(CURL_E_SHAPE, "grad_img must not alias img or coeffs");
   const int ro = (flags & CURL_F_RESIDUAL_ONLY) ? 1 : 0;
-  if (num_coeffs == 126) launch_trispace_img_grad<5>(img, coeffs, grad_out, grad_img, B, H, W, ro, (hipStream_t)stream);
+  if (num_coeffs == PolyEval<5>::kCoeffs) launch_trispace_img_grad<5>(img, coeffs, grad_out, grad_img, B, H, W, ro, (hipStream_t)stream);
   else launch_trispace_img_grad<3>(img, coeffs, grad_out, grad_img, B, H, W, ro, (hipStream_t)stream);
   return hip_done("trispace_img_grad_kernel");
 }

@@ -313,12 +313,7 @@ struct OpTriSpaceOrder : OpDefaults {
   static constexpr bool kSingleTileShape = true;
   static constexpr int kLdsFloats = 9 * PolyEval<V, D>::kSeqStride;
   static constexpr int kMinWavesPerSimd = kTriSpaceWaves;
-  // LDS position p of polynomial q holds the coefficient the Horner scheme consumes p-th
-  static __device__ __forceinline__ int stage_index(int i) {
-    constexpr int NC = PolyEval<V, D>::kCoeffs, NS = PolyEval<V, D>::kSeqStride;
-    int q = i / NS, pos = i - q * NS;
-    return q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0);  // padding slots are never read
-  }
+  static __device__ __forceinline__ int stage_index(int i) { return poly_seq_index<V, D>(i); }
   static constexpr bool kBlendMaskedOut = false;
   static __device__ __forceinline__ K load(const float* coef_img, const StreamArgs& a) {
     return K{coef_img, a.W, a.row0, (float)a.W, (float)a.H, a.op_flag != 0};
@@ -404,10 +399,8 @@ __device__ __forceinline__ void poly_layer_block(const float* in, const float* c
 #pragma unroll
   for (int k = 0; k < V; ++k) x[k] = ld<true>(p + (size_t)k * plane);  // before the staging barrier
   const float* table = coeffs + (size_t)img * 3 * NC;
-  for (int j = threadIdx.x; j < 3 * NS; j += 256) {
-    const int q = j / NS, pos = j - q * NS;
-    s_coef[j] = table[q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0)];  // padding slots are never read
-  }
+  // (unsigned: the index is never negative, and said so it is not sign-extended into the address)
+  for (int j = threadIdx.x; j < 3 * NS; j += 256) s_coef[j] = table[(unsigned)poly_seq_index<V, D>(j)];
   __syncthreads();
   if (i >= n) return;
   // VEC SCALAR Horner chains per lane in lock step (the generated scheme's pixel loop with F = float): they share every

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256, 2) void trispace_bwd_px_kernel(const float* im
   __shared__ __attribute__((aligned(16))) float s_coef[9 * NS];
   const unsigned b = blockIdx.y;
   const float* table = coeffs + (size_t)b * 9 * NC;
-  for (int i = threadIdx.x; i < 9 * NS; i += 256) s_coef[i] = table[OpTriSpace<V>::stage_index(i)];
+  for (int i = threadIdx.x; i < 9 * NS; i += 256) s_coef[i] = table[poly_seq_index<V>(i)];
   __syncthreads();
   const unsigned i0 = (blockIdx.x * 256u + threadIdx.x) * N;
   if (i0 >= HW) return;

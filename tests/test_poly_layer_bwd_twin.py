@@ -11,38 +11,22 @@ its results:
                         the tile rows are float64 in both), torch sums pairwise: (64 + 256) / ~3 -> next power of two    k = 128
 and never more than the project's polynomial-backward ceiling of 2e-4."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import HIP_CLANG, ROOT
 from poly_layer_bwd_ref import CEILING, case, rel
+from twin_build import FLAVOURS, twin_library
 
 K_IMG, K_COEF = 32, 128
 FLOOR = 2.0 ** -24
 
 
-@pytest.fixture(scope="module", params=["rounding", "contracting"])
+@pytest.fixture(scope="module", params=FLAVOURS)
 def bwd_twin(request):
     """The two flavours of conftest's `twin` fixture, for this twin's own source file."""
-    if request.param == "rounding":
-        name, cmd = "libpoly_layer_bwd_twin.so", ["g++", "-O2", "-mfma", "-ffp-contract=off"]
-    else:
-        if not os.path.exists(HIP_CLANG):
-            pytest.skip("hipcc's clang is not installed here")
-        name, cmd = "libpoly_layer_bwd_twin_contracting.so", [HIP_CLANG, "-O2", "-mfma", "-ffp-contract=fast-honor-pragmas"]
-    src = os.path.join(ROOT, "tests", "twin", "poly_layer_bwd_twin.cpp")
-    csrc = os.path.join(ROOT, "curl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))]
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name)
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(cmd + ["-fPIC", "-shared", "-std=c++17", "-DCURL_HOST_TWIN", "-Wno-unknown-pragmas", "-o", so, src])
-    return ctypes.CDLL(so)
+    return twin_library("poly_layer_bwd_twin.cpp", request.param)
 
 
 def _P(a):

@@ -12,7 +12,8 @@ import torch
 
 import curl_oracle as O
 import poly_orders_ref as R
-from conftest import HIP_CLANG, ROOT, max_err
+from conftest import ROOT, max_err
+from twin_build import FLAVOURS, twin_library
 
 E_NULL, E_SHAPE, E_KNOTS = -1, -2, -3
 
@@ -241,24 +242,10 @@ def test_malformed_tables_name_the_lower_order_widths(monkeypatch):
 
 
 # ------------------------------------------------------------------ the generated schemes and their host twin
-@pytest.fixture(scope="module", params=["rounding", "contracting"])
+@pytest.fixture(scope="module", params=FLAVOURS)
 def orders_twin(request):
     """The two flavours of conftest's `twin` fixture, for this twin's own source file."""
-    if request.param == "rounding":
-        name, cmd = "libpoly_orders_twin.so", ["g++", "-O2", "-mfma", "-ffp-contract=off"]
-    else:
-        if not os.path.exists(HIP_CLANG):
-            pytest.skip("hipcc's clang is not installed here")
-        name, cmd = "libpoly_orders_twin_contracting.so", [HIP_CLANG, "-O2", "-mfma", "-ffp-contract=fast-honor-pragmas"]
-    src = os.path.join(ROOT, "tests", "twin", "poly_orders_twin.cpp")
-    csrc = os.path.join(ROOT, "curl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))]
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name)
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(cmd + ["-fPIC", "-shared", "-std=c++17", "-DCURL_HOST_TWIN", "-Wno-unknown-pragmas", "-o", so, src])
-    return ctypes.CDLL(so)
+    return twin_library("poly_orders_twin.cpp", request.param)
 
 
 def _P(a):

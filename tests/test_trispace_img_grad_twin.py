@@ -11,34 +11,17 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import HIP_CLANG, ROOT
+from conftest import ROOT
 from trispace_img_grad_ref import case, case_8bit, check
+from twin_build import BUILD, COMMON, FLAVOURS, stale, twin_library
 
-SRC = os.path.join(ROOT, "tests", "twin", "trispace_img_grad_twin.cpp")
-CSRC = os.path.join(ROOT, "curl_amd", "csrc")
-BUILD = os.path.join(ROOT, "tests", "_build")
-COMMON = ["-std=c++17", "-DCURL_HOST_TWIN", "-Wno-unknown-pragmas"]
+SOURCE = "trispace_img_grad_twin.cpp"
 
 
-def _stale(out):
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps)
-
-
-@pytest.fixture(scope="module", params=["rounding", "contracting"])
+@pytest.fixture(scope="module", params=FLAVOURS)
 def grad_twin(request):
     """The two flavours of conftest's `twin` fixture, for this twin's own source file."""
-    if request.param == "rounding":
-        name, cmd = "libtrispace_img_grad_twin.so", ["g++", "-O2", "-mfma", "-ffp-contract=off"]
-    else:
-        if not os.path.exists(HIP_CLANG):
-            pytest.skip("hipcc's clang is not installed here")
-        name, cmd = "libtrispace_img_grad_twin_contracting.so", [HIP_CLANG, "-O2", "-mfma", "-ffp-contract=fast-honor-pragmas"]
-    os.makedirs(BUILD, exist_ok=True)
-    so = os.path.join(BUILD, name)
-    if _stale(so):
-        subprocess.check_call(cmd + ["-fPIC", "-shared"] + COMMON + ["-o", so, SRC])
-    return ctypes.CDLL(so)
+    return twin_library(SOURCE, request.param)
 
 
 def _twin_grad(lib, img, c, w, residual_only):
@@ -71,9 +54,10 @@ def test_twin_standalone_under_sanitizers():
     """The same source as a stand-alone program with its own main, built with AddressSanitizer and UBSan, run once."""
     exe = os.path.join(BUILD, "trispace_img_grad_twin_san")
     os.makedirs(BUILD, exist_ok=True)
-    if _stale(exe):
+    src = os.path.join(ROOT, "tests", "twin", SOURCE)
+    if stale(exe, src):
         subprocess.check_call(["g++", "-O1", "-g", "-mfma", "-ffp-contract=off", "-fsanitize=address,undefined",
-                               "-fno-sanitize-recover=undefined", "-DTWIN_MAIN"] + COMMON + ["-o", exe, SRC])
+                               "-fno-sanitize-recover=undefined", "-DTWIN_MAIN"] + COMMON + ["-o", exe, src])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
     assert p.stdout.count("sum") == 4 and "runtime error" not in p.stderr

@@ -3,15 +3,13 @@ host twin of its own (tests/twin/pwl_twin.cpp), against float64 autograd through
 oracle's converters and stage order, each curve the gather form C_i + slope_i f of the paper): random inputs, 8-bit values
 with pixels on the knots, saturated inputs (clamps active), bool and soft masks, K = 2, 16 and 256 knots per curve."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import curl_oracle as O
-from conftest import HIP_CLANG, ROOT
+from twin_build import FLAVOURS, twin_library
 
 TOL = 2e-4  # knot gradients: relative to the largest; the image gradient: relative to its largest magnitude
 
@@ -117,24 +115,10 @@ def make_case(case, K, seed, B=2, H=12, W=20):
 
 
 # ------------------------------------------------------------------ the twin
-@pytest.fixture(scope="module", params=["rounding", "contracting"])
+@pytest.fixture(scope="module", params=FLAVOURS)
 def pwl_twin(request):
-    """Built with the rounding flags of conftest._twin (g++, no contraction) and with hipcc's clang contracting as the kernels'
-    compiler does."""
-    if request.param == "rounding":
-        cmd, name = ["g++", "-O2", "-mfma", "-ffp-contract=off"], "libpwl_twin.so"
-    else:
-        if not os.path.exists(HIP_CLANG):
-            pytest.skip("hipcc's clang is not installed here")
-        cmd, name = [HIP_CLANG, "-O2", "-mfma", "-ffp-contract=fast-honor-pragmas"], "libpwl_twin_contracting.so"
-    src = os.path.join(ROOT, "tests", "twin", "pwl_twin.cpp")
-    deps = [src] + [os.path.join(ROOT, "curl_amd", "csrc", h) for h in ("curl_math.h", "curl_math_bwd.h")]
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name)
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(cmd + ["-fPIC", "-shared", "-std=c++17", "-DCURL_HOST_TWIN", "-Wno-unknown-pragmas", "-o", so, src])
-    return ctypes.CDLL(so)
+    """The two flavours of conftest's `twin` fixture, for this twin's own source file."""
+    return twin_library("pwl_twin.cpp", request.param)
 
 
 def _f32(a):

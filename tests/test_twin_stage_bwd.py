@@ -3,37 +3,21 @@ lab_stage_bwd, hsv_stage_bwd, the converters' *_bwd, knots_bwd) on a host twin o
 against float64 autograd through the oracle: random inputs, 8-bit values with channel ties, saturated inputs (clamps
 active), bool and soft masks, knot counts torch.chunk splits unevenly."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import curl_oracle as O
-from conftest import HIP_CLANG, ROOT
+from twin_build import FLAVOURS, twin_library
 
 TOL = 2e-4  # tests/test_twin_bwd.py's
 
 
-@pytest.fixture(scope="module", params=["rounding", "contracting"])
+@pytest.fixture(scope="module", params=FLAVOURS)
 def stage_twin(request):
-    """Built with the rounding flags of conftest._twin (g++, no contraction) and with hipcc's clang contracting as the
-    kernels' compiler does."""
-    if request.param == "rounding":
-        cmd, name = ["g++", "-O2", "-mfma", "-ffp-contract=off"], "libstage_twin.so"
-    else:
-        if not os.path.exists(HIP_CLANG):
-            pytest.skip("hipcc's clang is not installed here")
-        cmd, name = [HIP_CLANG, "-O2", "-mfma", "-ffp-contract=fast-honor-pragmas"], "libstage_twin_contracting.so"
-    src = os.path.join(ROOT, "tests", "twin", "stage_twin.cpp")
-    deps = [src] + [os.path.join(ROOT, "curl_amd", "csrc", h) for h in ("curl_math.h", "curl_math_bwd.h")]
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, name)
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(cmd + ["-fPIC", "-shared", "-std=c++17", "-DCURL_HOST_TWIN", "-Wno-unknown-pragmas", "-o", so, src])
-    return ctypes.CDLL(so)
+    """The two flavours of conftest's `twin` fixture, for this twin's own source file."""
+    return twin_library("stage_twin.cpp", request.param)
 
 
 def _f32(a):

@@ -50,6 +50,7 @@ static void record(int line, const void* kernel, dim3 grid, dim3 block, unsigned
 #define hipGetLastError() hipSuccess
 
 #include "curl_kernels.hip"  // -I curl_amd/csrc (its own include of hip_runtime.h is guarded: the redefinitions hold)
+#include "../../include/curl_hip_poly.h"
 
 // what the host-only object still refers to: no-ops, so that no HIP runtime is linked
 extern "C" {
@@ -362,6 +363,7 @@ static void conv_bwd(int which, const std::string& label, const Conv& c) {
   }
 }
 
+constexpr int kPolyCounts[2][3] = {{4, 10, 20}, {6, 21, 56}};  // C(V + D, D) for V = 3 | 5, D = 1..3, said here on their own
 struct Tri {  // the polynomial model: forward, slab (rows > 0), byte edge, backward
   const float *img = IMG, *coef = COEF, *gout = GOUT;
   float *out = OUT, *gcoef = GCOEF;
@@ -719,6 +721,19 @@ static void stream_cases() {
   tri_u8("trispace u8: num_coeffs 34", WITH(Tri, c.nc = 34));
   tri_u8("trispace u8: any flag", WITH(Tri, c.flags = CURL_F_RESIDUAL_ONLY));
   tri_u8("trispace u8: coeffs off the 8-byte grid", WITH(Tri, c.coef = off(COEF, 4)));
+
+  // ---- orders 1-3 (curl_hip_poly.h): the order in the high half of num_coeffs, a kernel per (variables, order)
+  for (int V : {5, 3})
+    for (int D : {1, 2, 3}) tri(S("V %d order %d: float4", V, D), WITH(Tri, c.nc = CURL_POLY_COEFFS(kPolyCounts[V == 5][D - 1], D)));
+  tri("V 5 order 2: scalar, H*W % 4 != 0", WITH(Tri, c.nc = CURL_POLY_COEFFS(21, 2), c.H = 33, c.W = 7));
+  tri("V 5 order 3: slab row0 = 1", WITH(Tri, c.nc = CURL_POLY_COEFFS(56, 3), c.row0 = 1, c.rows = 7));
+  tri("V 5 order 4 said in the high half: the row-tiled kernel", WITH(Tri, c.nc = CURL_POLY_COEFFS(126, 4)));
+  tri_u8("V 5 order 1: float4, white mask", WITH(Tri, c.nc = CURL_POLY_COEFFS(6, 1)));
+  tri_u8("V 3 order 2: float4, no white mask", WITH(Tri, c.nc = CURL_POLY_COEFFS(10, 2)), U8IN, U8OUT, nullptr);
+  tri("trispace: order 5", WITH(Tri, c.nc = CURL_POLY_COEFFS(126, 5)));
+  tri("trispace: order 0", WITH(Tri, c.nc = CURL_POLY_COEFFS(126, 0)));
+  tri("trispace: a count of another order, CURL_POLY_COEFFS(56, 2)", WITH(Tri, c.nc = CURL_POLY_COEFFS(56, 2)));
+  tri_u8("trispace u8: a plain 56, no order in the high half", WITH(Tri, c.nc = 56));
 }
 
 static void pointwise_cases() {
@@ -734,6 +749,14 @@ static void pointwise_cases() {
   poly("poly_layer: out NULL", WITH(Poly, c.out = nullptr));
   poly("poly_layer: coeffs NULL", WITH(Poly, c.coef = nullptr));
   poly("poly_layer: num_variables 4", WITH(Poly, c.V = 4));
+  // degrees 1-3 (curl_hip_poly.h): the degree in the high half of num_variables
+  for (int V : {5, 3})
+    for (int D : {1, 2, 3}) poly(S("V %d degree %d: float4", V, D), WITH(Poly, c.V = CURL_POLY_VARS(V, D)));
+  poly("V 3 degree 2: scalar, H*W % 4 != 0", WITH(Poly, c.V = CURL_POLY_VARS(3, 2), c.H = 33, c.W = 7));
+  poly("V 5 degree 4 said in the high half", WITH(Poly, c.V = CURL_POLY_VARS(5, 4)));
+  poly("poly_layer: degree 5", WITH(Poly, c.V = CURL_POLY_VARS(5, 5)));
+  poly("poly_layer: degree 0", WITH(Poly, c.V = CURL_POLY_VARS(5, 0)));
+  poly("poly_layer: 4 variables with a degree", WITH(Poly, c.V = CURL_POLY_VARS(4, 2)));
 
   // ---- the layout edges
   const auto ingress = [](const std::string& l, const Shape& s, int Cin, const uint8_t* in = U8IN, float* out = OUT) {

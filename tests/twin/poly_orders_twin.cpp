@@ -17,10 +17,7 @@ static void layer(const float* img, const float* coeffs, float* out, int B, long
   for (int b = 0; b < B; ++b) {
     const float* table = coeffs + (size_t)b * 3 * NC;
     float staged[3 * NS];
-    for (int j = 0; j < 3 * NS; ++j) {  // as poly_layer_kernel / OpTriSpace::stage_index fill the LDS copy
-      const int q = j / NS, pos = j - q * NS;
-      staged[j] = table[q * NC + PolyEval<V, D>::order(pos < NC ? pos : 0)];
-    }
+    for (int j = 0; j < 3 * NS; ++j) staged[j] = table[poly_seq_index<V, D>(j)];  // the kernels' own staging rule
     for (long i = 0; i < HW; ++i) {
       float v[V][1], o[3][1];
       for (int k = 0; k < V; ++k) v[k][0] = img[((size_t)b * V + k) * HW + i];
