@@ -505,30 +505,33 @@ def msssim(img1, img2, window_size=11, num_channel=3):
     return torch.prod(pow1[:, :-1] * pow2[:, -1].reshape(-1, 1), dim=1)
 
 
-def input_sensitivity(img, mask, L, R, H, r64=None, h=1e-6):
+def input_sensitivity(img, mask, L, R, H, r64=None, h=1e-6, *, num_lab_points=48, num_rgb_points=48, num_hsv_points=64):
     """Conditioning of the chain at every pixel: max over the three input channels and both signs of
     |d out / d in|, by finite differences of curl_layer evaluated in float64 -- how much model.py:137-176 amplifies a
     rounding-sized perturbation there.  -> [B,H,W] float64.  The parity bound |HIP - ref| <= max(1e-5, 2e-6 * S) is
-    stated on it (tests/test_gpu_parity.py, __graft_entry__.smoke, bench.py accuracy)."""
+    stated on it (tests/test_gpu_parity.py, __graft_entry__.smoke, bench.py accuracy).
+    num_*_points: the raw parameters per segment, as curl_layer takes them (torch.chunk splits an uneven total)."""
+    n = (num_lab_points, num_rgb_points, num_hsv_points)
     img, mask, L, R, H = (t.double() for t in (img, mask, L, R, H))
     if r64 is None:
-        r64, _ = curl_layer(img, mask, L, R, H)
+        r64, _ = curl_layer(img, mask, L, R, H, *n)
     S = torch.zeros(r64.shape[0], r64.shape[2], r64.shape[3], dtype=torch.float64)
     for k in range(3):
         for sgn in (1.0, -1.0):
             p = img.clone()
             p[:, k] += sgn * h
-            o, _ = curl_layer(p, mask, L, R, H)
+            o, _ = curl_layer(p, mask, L, R, H, *n)
             S = torch.maximum(S, (o - r64).abs().amax(1) / h)
     return S
 
 
-def layer_gradients(img, mask, L, R, H, w, wr=None, dtype=torch.float64):
+def layer_gradients(img, mask, L, R, H, w, wr=None, dtype=torch.float64, *, num_lab_points=48, num_rgb_points=48,
+                    num_hsv_points=64):
     """Autograd of curl_layer (the reference's arithmetic, model.py:137-176) for the loss sum(out * w) + sum(reg * wr),
     evaluated in `dtype`.  -> (d img, d L, d R, d H).  The float64 evaluation is the backward's parity yardstick."""
     x = img.detach().to(dtype).clone().requires_grad_(True)
     Lk, Rk, Hk = (t.detach().to(dtype).clone().requires_grad_(True) for t in (L, R, H))
-    out, reg = curl_layer(x, mask.to(dtype), Lk, Rk, Hk)
+    out, reg = curl_layer(x, mask.to(dtype), Lk, Rk, Hk, num_lab_points, num_rgb_points, num_hsv_points)
     loss = (out * w.to(dtype)).sum()
     if wr is not None:
         loss = loss + (reg * wr.to(dtype)).sum()
@@ -536,20 +539,21 @@ def layer_gradients(img, mask, L, R, H, w, wr=None, dtype=torch.float64):
     return x.grad, Lk.grad, Rk.grad, Hk.grad
 
 
-def gradient_curvature(img, mask, L, R, H, w, g64=None, h=1e-6):
+def gradient_curvature(img, mask, L, R, H, w, g64=None, h=1e-6, *, num_lab_points=48, num_rgb_points=48, num_hsv_points=64):
     """How fast the image gradient itself changes with the input, per pixel: max over the three channels and both signs of
     |d img(x +- h e_k) - d img(x)| / h, float64 -- the backward's counterpart of input_sensitivity.  A float32 evaluation of
     the chain sees its intermediates perturbed by roundings worth ~1e-6 of input; its gradient can be off by that times this
     curvature.  A pixel whose value h * curvature is a sizeable fraction of the gradient scale sits within h of a clamp gate, a
     threshold or a channel tie -- a DISCONTINUITY of the gradient: the exception set of tests/test_gpu_backward.py.
     -> [B,H,W] float64."""
+    n = dict(num_lab_points=num_lab_points, num_rgb_points=num_rgb_points, num_hsv_points=num_hsv_points)
     if g64 is None:
-        g64 = layer_gradients(img, mask, L, R, H, w)[0]
+        g64 = layer_gradients(img, mask, L, R, H, w, **n)[0]
     C = torch.zeros(g64.shape[0], g64.shape[2], g64.shape[3], dtype=torch.float64)
     for k in range(3):
         for sgn in (1.0, -1.0):
             p = img.double().clone()
             p[:, k] += sgn * h
-            gp = layer_gradients(p, mask, L, R, H, w)[0]
+            gp = layer_gradients(p, mask, L, R, H, w, **n)[0]
             C = torch.maximum(C, (gp - g64).abs().amax(1) / h)
     return C

@@ -73,8 +73,13 @@ MASKS = ["none", "bool", "u8", "f32"]
 @pytest.mark.parametrize("mask_kind,mask_first", [(k, False) for k in MASKS] + [("bool", True), ("u8", True)])
 @pytest.mark.parametrize("W", [20, 21])  # float4 path, scalar path (odd W)
 def test_pwl_backward_vs_oracle(ops, dev, K, mask_kind, mask_first, W):
+    backward_vs_oracle(ops, dev, K, mask_kind, mask_first, W, 40 + K + W + MASKS.index(mask_kind))
+
+
+def backward_vs_oracle(ops, dev, K, mask_kind, mask_first, W, seed):
+    """K: knots per curve, one count or (Kl, Kr, Kh) (tests/test_gpu_knot_paths.py runs this body off K = 16 and 64)."""
     case = {"none": "random", "bool": "boolmask", "u8": "boolmask", "f32": "softmask"}[mask_kind]
-    img, mask, L, R, Hk, gout, greg = _case(case, K, 40 + K + W + MASKS.index(mask_kind), W)
+    img, mask, L, R, Hk, gout, greg = _case(case, K, seed, W)
     if mask is not None and mask_kind in ("bool", "u8"):
         mask[0] = 0  # a whole image masked out: every wavefront of it takes the dead-wave skip
     m = _gpu_mask(mask, mask_kind, dev)

@@ -94,9 +94,12 @@ def knot_tol(want32, want):
 
 
 def make_case(case, K, seed, B=2, H=12, W=20):
+    """K: knots per curve, one count or one per segment (Kl, Kr, Kh)."""
+    Kl, Kr, Kh = (K, K, K) if isinstance(K, int) else K
     g = torch.Generator().manual_seed(seed)
     img = torch.rand(B, 3, H, W, generator=g)
     if case == "grid8":
+        K = Kr
         img = torch.randint(0, 256, (B, 3, H, W), generator=g).float() / 255
         # pixels exactly on knots of the RGB curves' inputs where the 8-bit grid has them (k / (K-1) = b / 255)
         img[:, :, :2] = (torch.randint(0, K, (B, 3, 2, W), generator=g) * (255 // (K - 1) if 255 % (K - 1) == 0 else 0)).float() / 255
@@ -107,7 +110,7 @@ def make_case(case, K, seed, B=2, H=12, W=20):
         mask = (torch.rand(B, 1, H, W, generator=g) > 0.3).float()
     if case == "softmask":
         mask, binary = torch.rand(B, 1, H, W, generator=g), False
-    L, R, Hk = (smooth_knots(B, n, K, g) for n in (3, 3, 4))
+    L, R, Hk = (smooth_knots(B, n, k, g) for n, k in ((3, Kl), (3, Kr), (4, Kh)))
     gout = torch.randn(B, 3, H, W, generator=g)
     greg = torch.rand(B, generator=g)
     return (img.numpy(), None if mask is None else mask.numpy(), binary, L.numpy(), R.numpy(), Hk.numpy(), gout.numpy(),
