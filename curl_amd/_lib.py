@@ -112,6 +112,15 @@ SIGNATURES_GRAD = {
     "curl_trispace_bwd_img_f32": (_i, [_c_f, _c_f, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),
 }
 
+# include/curl_hip_view.h: the encoder's view from image bytes (a third table, for the same reason; the two plan functions take
+# and fill HOST memory and make no HIP call)
+SIGNATURES_VIEW = {
+    "curl_encoder_view_plan_bytes": (_sz, [_i, _i, _i]),
+    "curl_encoder_view_plan": (_i, [_i, _i, _i, _c_f, _sz]),
+    "curl_encoder_view_u8hwc": (_i, [_c_f, _i, _c_f, _c_f, _sz, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),
+}
+VIEW_SIZE_DEFAULT = 320  # CURL_VIEW_SIZE_DEFAULT
+
 _lib = None
 
 
@@ -134,7 +143,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

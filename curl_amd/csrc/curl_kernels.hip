@@ -18,9 +18,11 @@
 
 #include "../../include/curl_hip.h"
 #include "../../include/curl_hip_grad.h"
+#include "../../include/curl_hip_view.h"
 #include "curl_math_bwd.h"
 #include "curl_math_poly.h"
 #include "curl_math_loss.h"
+#include "curl_math_view.h"
 
 using namespace curlm;
 
@@ -213,5 +215,7 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/trispace_img_grad.inc"
 #include "kernels/loss.inc"
 #include "kernels/edges.inc"
+#include "kernels/encoder_view.inc"
 #include "kernels/host_api.inc"
 #include "kernels/host_api_grad.inc"
+#include "kernels/host_api_view.inc"

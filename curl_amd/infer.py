@@ -32,7 +32,9 @@ def build_net(model_file, device, arch="curl", polynomial_order=4):
 
 
 def encoder_view(img, mask, size=320):
-    """Resize([320]) (short side) + CenterCrop(320) of infer.py:32-36, on the device."""
+    """Resize([320]) (short side) + CenterCrop(320) of infer.py:32-36, on the device, in float: torch's antialiased
+    interpolate on the float image (the `view="float"` route of enhance; ops.encoder_view_u8hwc is the reference's own
+    arithmetic on the bytes)."""
     _, _, H, W = img.shape
     scale = size / min(H, W)
     nh, nw = max(size, round(H * scale)), max(size, round(W * scale))
@@ -43,16 +45,24 @@ def encoder_view(img, mask, size=320):
 
 
 @torch.no_grad()
-def enhance(net, img_u8, mask_u8, device):
+def enhance(net, img_u8, mask_u8, device, view="float"):
     """img_u8: HxWx3|4 uint8, mask_u8: HxW uint8 ('L').  Returns HxWx3 uint8 (numpy).
     The full-resolution pass runs on the file's own bytes (ops.*_u8hwc: byte/255, the model's per-pixel part, the
-    white background and the truncating *255 in one launch); only the 320x320 encoder view is made in float."""
+    white background and the truncating *255 in one launch).  The 320x320 encoder view:
+      view="float"  made in float from the converted full-resolution image (encoder_view above);
+      view="pil"    the reference's own view -- Pillow's 8-bit resample of the bytes, bit for bit -- in one launch
+                    (ops.encoder_view_u8hwc); no full-resolution float image is made at all."""
+    if view not in ("float", "pil"):
+        raise ValueError(f"view must be 'float' or 'pil', got {view!r}")
     rgb = torch.from_numpy(np.ascontiguousarray(np.asarray(img_u8)[..., :3])).to(device)[None]  # alpha dropped
     white = torch.from_numpy(np.array(mask_u8, dtype=np.uint8)).to(device)[None]
-    x = ops.u8hwc_to_f32chw(rgb)
-    tmask = white[:, None].float() / 255.0  # to_tensor
-    small, msmall = encoder_view(x, tmask)
-    del x
+    if view == "pil":
+        small, msmall = ops.encoder_view_u8hwc(rgb, white)  # infer.py:32-41
+    else:
+        x = ops.u8hwc_to_f32chw(rgb)
+        tmask = white[:, None].float() / 255.0  # to_tensor
+        small, msmall = encoder_view(x, tmask)
+        del x
     if isinstance(net, model_mod.TriSpaceRegNet):
         coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)       # infer.py:44, model.py:522-527
         return ops.trispace_forward_u8hwc(rgb, coeffs, white)[0].cpu().numpy()  # infer.py:44-47
@@ -77,6 +87,9 @@ def infer(argv=None):
                              "curl = the curve model (GCURLNet)")
     parser.add_argument("--polynomial_order", type=int, default=4, choices=(1, 2, 3, 4),
                         help="trispace: the polynomial_order the checkpoint was trained with (model.py:439)")
+    parser.add_argument("--encoder_view", choices=("float", "pil"), default="float",
+                        help="how the encoder's 320x320 input is made: float = torch's antialiased interpolate on the float "
+                             "image; pil = the reference's Pillow resample of the bytes, bit for bit, in one HIP launch")
     args = parser.parse_args(argv)
     from PIL import Image
     device = torch.device("cuda:0")
@@ -85,7 +98,7 @@ def infer(argv=None):
     if img.ndim == 2:
         img = np.repeat(img[..., None], 3, axis=2)
     mask = np.asarray(Image.open(args.mask_path).convert("L"))
-    out = enhance(net, img, mask, device)
+    out = enhance(net, img, mask, device, view=args.encoder_view)
     Image.fromarray(out).save(args.out_path)
 
 

@@ -99,7 +99,7 @@ def _one_device(fn):
 # keyword arguments that carry no tensor, or one whose device the body checks itself against the image's (`out`: _check_out,
 # `workspace`: curl_layer_backward); any other tensor passed by keyword takes the slow, fully checked path
 _PLAIN_KWARGS = frozenset(("flags", "return_workspace", "residual_only", "need_grad_img", "need_img_grad", "need_coeffs_grad", "max_intensity", "window_size",
-                           "want_L", "out", "workspace"))
+                           "want_L", "out", "workspace", "size"))
 
 
 def _coeffs32(coeffs, pairs=True):
@@ -987,6 +987,56 @@ def curl_layer_forward_u8hwc(img_u8, mask, L, R, H, white_mask=None):
                                   _stream(x))
     _lib.check(rc, "curl_layer_fwd_u8hwc")
     return out, reg
+
+
+_view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
+_VIEW_PLANS_KEPT = 16
+
+
+def _view_plan(H, W, size, device):
+    """The coefficient tables of one shape on the device: built on the host by the library, uploaded once, kept for the
+    next frames of that shape (the oldest of more than sixteen shapes is dropped)."""
+    key = (H, W, size, device)
+    plan = _view_plans.get(key)
+    if plan is None:
+        lib = _lib.load()
+        nbytes = lib.curl_encoder_view_plan_bytes(H, W, size)
+        host = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32)
+        _lib.check(lib.curl_encoder_view_plan(H, W, size, host.data_ptr(), nbytes), "curl_encoder_view_plan")
+        if len(_view_plans) >= _VIEW_PLANS_KEPT:
+            del _view_plans[next(iter(_view_plans))]
+        plan = _view_plans[key] = host.to(device)
+    return plan
+
+
+@_one_device
+def encoder_view_u8hwc(img_u8, mask_u8=None, size=_lib.VIEW_SIZE_DEFAULT):
+    """The encoder's input as the reference makes it (infer.py:32-41), from the decoded bytes in one launch: torchvision's
+    Resize([size]) + CenterCrop((size, size)) -- Pillow's 8-bit antialiased bilinear resample, bit for bit -- then to_tensor.
+    img_u8 uint8 [B,H,W,3|4] (alpha is not read), mask_u8 uint8 [B,H,W] or None
+    -> (view float32 [B,3,size,size], mask_view float32 [B,1,size,size] = (resampled mask byte > 0), or None)."""
+    lib = _lib.load()
+    _need_device(img_u8, "img_u8")
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[3] not in (3, 4):
+        raise ValueError(f"img_u8 must be uint8 [B,H,W,3|4], got {img_u8.dtype} {tuple(img_u8.shape)}")
+    if img_u8.numel() == 0:
+        raise ValueError(f"img_u8 is empty: {tuple(img_u8.shape)}")
+    x = img_u8.contiguous()
+    B, H, W, C = x.shape
+    m = None
+    if mask_u8 is not None:
+        _need_device(mask_u8, "mask_u8")
+        if mask_u8.dtype != torch.uint8 or tuple(mask_u8.shape) != (B, H, W):
+            raise ValueError(f"mask_u8 must be uint8 [B,H,W] ('L' image), got {mask_u8.dtype} {tuple(mask_u8.shape)}")
+        m = mask_u8.contiguous()
+    size = int(size)
+    plan = _view_plan(H, W, size, x.device)
+    view = torch.empty(B, 3, size, size, dtype=torch.float32, device=x.device)
+    mview = torch.empty(B, 1, size, size, dtype=torch.float32, device=x.device) if m is not None else None
+    rc = lib.curl_encoder_view_u8hwc(x.data_ptr(), C, _ptr(m), plan.data_ptr(), plan.numel() * 4, view.data_ptr(), _ptr(mview),
+                                     B, H, W, size, 0, _stream(x))
+    _lib.check(rc, "curl_encoder_view_u8hwc")
+    return view, mview
 
 
 def _planes(t, name):
