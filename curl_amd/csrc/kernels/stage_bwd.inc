@@ -58,7 +58,22 @@ __global__ __launch_bounds__(256) void stage_bwd_kernel(BwdArgs a) {
       if (!tile.valid()) gin = Px{0.0f, 0.0f, 0.0f}, m = 0.0f;
       // one pixel after the other (bwd_tile.inc, at BwdTile::m)
       asm volatile("" : "+v"(pin.c0), "+v"(pin.c1), "+v"(pin.c2), "+v"(gin.c0), "+v"(gin.c1), "+v"(gin.c2) : "v"(dep));
-      Px gi = stage_pixel_bwd<OP, MK != CURL_MASK_F32, GIN>(pin, m, k, gin, acc, acc + NC);
+      // P: each pixel's terms from zero, then one plain add behind a barrier.  `P += g_pre * x` (curve_self_pull,
+      // curve_cross_pull) is the compiler's to contract, and it chose per instantiation: with four pixels per lane the GIN
+      // and !GIN kernels of the four-curve operators fused different ones of these, and need_grad_img=False moved the knot
+      // gradient's last bits (tests/test_gpu_pixel_jacobians.py).  From zero both forms are the rounded product; Q's fmaf is
+      // explicit and the same everywhere.  This rests on every pullback adding exactly ONE term per pixel to each P[c]
+      // (curve_self_pull and curve_cross_pull, each called once per curve): a second `+=` into the same P[c] within a pixel
+      // would be contractable again.
+      float pp[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) pp[c] = 0.0f;
+      Px gi = stage_pixel_bwd<OP, MK != CURL_MASK_F32, GIN>(pin, m, k, gin, pp, acc + NC);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        asm("" : "+v"(pp[c]));
+        acc[c] += pp[c];
+      }
       dep = gi.c0;
       if constexpr (GIN) {
         set_lane(y0, e, gi.c0);

@@ -6,10 +6,16 @@ import pytest
 import torch
 
 import curl_oracle as O
+import jacobian_check as JC
 from conftest import has_gpu
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a HIP device")]
 TOL = 2e-4  # tests/test_twin_bwd.py's
+SMALLEST = (2, 7, 9)
+JC_KIND = {"random": "random", "grid8": "grid8", "saturated": "wide"}  # jacobian_check's content for a case here
+# ... drawn with a seed at which every operator's 126 pixels meet the input conditions (one pixel is 0.8 % there; 8-bit hues of
+# exactly 85 / 255 and 170 / 255 are near kinks of hsv2rgb, and the default draw holds two of them)
+JC_SEED = 4
 
 
 @pytest.fixture(scope="module")
@@ -122,6 +128,17 @@ def test_curve_ops_vs_oracle(ops, dev, op, case, shape):
         if case != "grid8":
             raise
         check_knot_grad(gk, wk, (op, case, shape), 2 * knot_conditioning(op, img, None, raw, w, wr, wk))
+    if shape == SMALLEST:
+        # the autograd node (_curve_op_grad) under tests/jacobian_check.py's per-pixel bar: one-hot w, the smallest shape
+        # (input conditions asserted by JC.case_references before the kernel runs)
+        ref, = JC.case_references(op, JC_KIND[case], "s03", shape, seed=JC_SEED)
+
+        def rows(go):
+            gi, gk = ours(ops, op, ref.x, None, ref.raw, go, wr, dev, use_reg=False)
+            return gi.cpu(), gk.cpu()
+        J, K = JC.one_hot_jacobian(rows, shape)
+        ref.check(J)
+        ref.check_knots(K)
 
 
 @pytest.mark.parametrize("mask_first", [False, True])
@@ -154,6 +171,15 @@ def test_converters_vs_oracle(dev, name, cls, case):
             (getattr(O, name)(y) * w.to(dt)).sum().backward()
             want[dt] = y.grad
         check_image_grad(x.grad, want[torch.float64], (name, case, shape), want[torch.float32])
+    # the autograd node (_ConvertFn) under tests/jacobian_check.py's per-pixel bar: one-hot w, the smallest shape (input
+    # conditions asserted by JC.case_references before the kernel runs)
+    ref, = JC.case_references(name, JC_KIND[case], None, SMALLEST, seed=JC_SEED)
+
+    def rows(go):
+        x = ref.x.to(dev).requires_grad_(True)
+        (mod(x) * go.to(dev)).sum().backward()
+        return x.grad.cpu()
+    ref.check(JC.one_hot_jacobian(rows, SMALLEST))
 
 
 @pytest.mark.parametrize("op", ["adjust_rgb", "adjust_lab", "adjust_hsv"])
