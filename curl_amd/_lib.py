@@ -121,6 +121,12 @@ SIGNATURES_VIEW = {
 }
 VIEW_SIZE_DEFAULT = 320  # CURL_VIEW_SIZE_DEFAULT
 
+# include/curl_hip_fg.h: the foreground-aware byte paths (a fourth table, for the same reason)
+SIGNATURES_FG = {
+    "curl_trispace_fwd_fg_u8hwc": (_i, [_c_f, _i, _c_f, _c_f, _c_f, _i, _i, _i, _i, _u, _c_f]),
+    "curl_layer_fwd_fg_u8hwc": (_i, [_c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _i, _i, _i, _i, _i, _i, _u, _c_f]),
+}
+
 _lib = None
 
 
@@ -143,7 +149,8 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
+            list(SIGNATURES_FG.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

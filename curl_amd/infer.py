@@ -45,16 +45,22 @@ def encoder_view(img, mask, size=320):
 
 
 @torch.no_grad()
-def enhance(net, img_u8, mask_u8, device, view="float"):
+def enhance(net, img_u8, mask_u8, device, view="float", foreground=False):
     """img_u8: HxWx3|4 uint8, mask_u8: HxW uint8 ('L').  Returns HxWx3 uint8 (numpy).
     The full-resolution pass runs on the file's own bytes (ops.*_u8hwc: byte/255, the model's per-pixel part, the
     white background and the truncating *255 in one launch).  The 320x320 encoder view:
       view="float"  made in float from the converted full-resolution image (encoder_view above);
       view="pil"    the reference's own view -- Pillow's 8-bit resample of the bytes, bit for bit -- in one launch
-                    (ops.encoder_view_u8hwc); no full-resolution float image is made at all."""
+                    (ops.encoder_view_u8hwc); no full-resolution float image is made at all.
+    foreground=True: the mask is a segmentation mask.  The image goes up with the channel count the file has (no host-side
+    slice of an RGBA image) and the full-resolution pass is ops.*_foreground_u8hwc: wavefronts the white background overwrites
+    entirely never read their pixels.  The same bytes come back."""
     if view not in ("float", "pil"):
         raise ValueError(f"view must be 'float' or 'pil', got {view!r}")
-    rgb = torch.from_numpy(np.ascontiguousarray(np.asarray(img_u8)[..., :3])).to(device)[None]  # alpha dropped
+    if foreground:
+        rgb = torch.from_numpy(np.ascontiguousarray(np.asarray(img_u8)[..., :4])).to(device)[None]  # RGB or RGBA, as is
+    else:
+        rgb = torch.from_numpy(np.ascontiguousarray(np.asarray(img_u8)[..., :3])).to(device)[None]  # alpha dropped
     white = torch.from_numpy(np.array(mask_u8, dtype=np.uint8)).to(device)[None]
     if view == "pil":
         small, msmall = ops.encoder_view_u8hwc(rgb, white)  # infer.py:32-41
@@ -65,11 +71,17 @@ def enhance(net, img_u8, mask_u8, device, view="float"):
         del x
     if isinstance(net, model_mod.TriSpaceRegNet):
         coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)       # infer.py:44, model.py:522-527
+        if foreground:
+            return ops.trispace_foreground_u8hwc(rgb, coeffs, white)[0].cpu().numpy()
         return ops.trispace_forward_u8hwc(rgb, coeffs, white)[0].cpu().numpy()  # infer.py:44-47
     knots = net.predict_knots(small * msmall)  # the encoder sees the masked 320x320 view
     L, R, H = knots[:, :net.curve_break_1], knots[:, net.curve_break_1:net.curve_break_2], knots[:, net.curve_break_2:]
     # the reference applies the mask only when compositing (infer.py:44-46): no layer mask
     cl = net.curllayer
+    if foreground:
+        out, _ = ops.curl_layer_foreground_u8hwc(rgb, L[:, :cl.num_lab_points].contiguous(), R[:, :cl.num_rgb_points].contiguous(),
+                                                 H[:, :cl.num_hsv_points].contiguous(), white)
+        return out[0].cpu().numpy()
     out, _ = ops.curl_layer_forward_u8hwc(rgb, None, L[:, :cl.num_lab_points].contiguous(),
                                           R[:, :cl.num_rgb_points].contiguous(),
                                           H[:, :cl.num_hsv_points].contiguous(), white)
@@ -90,6 +102,9 @@ def infer(argv=None):
     parser.add_argument("--encoder_view", choices=("float", "pil"), default="float",
                         help="how the encoder's 320x320 input is made: float = torch's antialiased interpolate on the float "
                              "image; pil = the reference's Pillow resample of the bytes, bit for bit, in one HIP launch")
+    parser.add_argument("--foreground_masks", action="store_true",
+                        help="the mask is a segmentation mask: regions it whites out entirely are never read or computed "
+                             "(the same output bytes)")
     args = parser.parse_args(argv)
     from PIL import Image
     device = torch.device("cuda:0")
@@ -98,7 +113,7 @@ def infer(argv=None):
     if img.ndim == 2:
         img = np.repeat(img[..., None], 3, axis=2)
     mask = np.asarray(Image.open(args.mask_path).convert("L"))
-    out = enhance(net, img, mask, device, view=args.encoder_view)
+    out = enhance(net, img, mask, device, view=args.encoder_view, foreground=args.foreground_masks)
     Image.fromarray(out).save(args.out_path)
 
 

@@ -989,6 +989,55 @@ def curl_layer_forward_u8hwc(img_u8, mask, L, R, H, white_mask=None):
     return out, reg
 
 
+def _bytes_image_fg(x, fg_mask):
+    """The foreground entries' image and mask: uint8 [B,H,W,3|4] (alpha is not read) and uint8 [B,H,W], required."""
+    _need_device(x, "img_u8")
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] not in (3, 4):
+        raise ValueError(f"img_u8 must be uint8 [B,H,W,3|4] (PIL's RGB / RGBA layout), got {x.dtype} {tuple(x.shape)}")
+    if x.numel() == 0:
+        raise ValueError(f"img_u8 is empty: {tuple(x.shape)}")
+    if fg_mask is None:
+        raise ValueError("fg_mask is required (uint8 [B,H,W], the 'L' mask)")
+    _need_device(fg_mask, "fg_mask")
+    if fg_mask.dtype != torch.uint8 or tuple(fg_mask.shape) != tuple(x.shape[:3]):
+        raise ValueError(f"fg_mask must be uint8 [B,H,W] ('L' image), got {fg_mask.dtype} {tuple(fg_mask.shape)}")
+    return x.contiguous(), fg_mask.contiguous()
+
+
+@_one_device
+def trispace_foreground_u8hwc(img_u8, coeffs, fg_mask):
+    """trispace_forward_u8hwc with white_mask = fg_mask for a segmentation mask, byte for byte the same result: wavefronts
+    whose mask bytes are all 0 store white and never read their pixels (curl_trispace_fwd_fg_u8hwc).
+    img_u8 uint8 [B,H,W,3|4] (alpha is not read), fg_mask uint8 [B,H,W] -> uint8 [B,H,W,3]."""
+    lib = _lib.load()
+    x, fg = _bytes_image_fg(img_u8, fg_mask)
+    B, H, W, C = x.shape
+    _check_coeffs(coeffs, B)
+    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=x.device)
+    rc = lib.curl_trispace_fwd_fg_u8hwc(x.data_ptr(), C, c.data_ptr(), fg.data_ptr(), out.data_ptr(), B, H, W,
+                                        _nc_arg(c.shape[3]), 0, _stream(x))
+    _lib.check(rc, "curl_trispace_fwd_fg_u8hwc")
+    return out
+
+
+@_one_device
+def curl_layer_foreground_u8hwc(img_u8, L, R, H, fg_mask):
+    """curl_layer_forward_u8hwc(img, None, L, R, H, white_mask=fg_mask) for a segmentation mask, byte for byte the same result
+    and the same reg (curl_layer_fwd_fg_u8hwc).  img_u8 uint8 [B,H,W,3|4] -> (uint8 [B,H,W,3], reg [B])."""
+    lib = _lib.load()
+    x, fg = _bytes_image_fg(img_u8, fg_mask)
+    B, Hh, W, C = x.shape
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
+    out = torch.empty(B, Hh, W, 3, dtype=torch.uint8, device=x.device)
+    reg = torch.empty(B, dtype=torch.float32, device=x.device)
+    ws, nbytes = _workspace(B, n_knots, x.device)
+    rc = lib.curl_layer_fwd_fg_u8hwc(x.data_ptr(), C, Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(), fg.data_ptr(), out.data_ptr(),
+                                     reg.data_ptr(), ws.data_ptr(), nbytes, B, Hh, W, Kl, Kr, Kh, 0, _stream(x))
+    _lib.check(rc, "curl_layer_fwd_fg_u8hwc")
+    return out, reg
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
