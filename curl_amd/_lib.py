@@ -127,6 +127,19 @@ SIGNATURES_FG = {
     "curl_layer_fwd_fg_u8hwc": (_i, [_c_f, _i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _sz, _i, _i, _i, _i, _i, _i, _u, _c_f]),
 }
 
+# include/curl_hip_ragged.h: a batch of images of different sizes in one launch per class (a fifth table, for the same reason;
+# the plan functions take and fill HOST memory and make no HIP call)
+SIGNATURES_RAGGED = {
+    "curl_ragged_plan_bytes": (_sz, [_i, _i]),
+    "curl_ragged_plan": (_i, [_i, _c_f, _c_f, _c_f, _i, _i, _c_f, _sz]),
+    "curl_ragged_arena_bytes": (_i, [_c_f, _c_f, _c_f, _c_f]),
+    "curl_trispace_fwd_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _i, _u, _c_f]),
+    "curl_layer_fwd_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _c_f, _c_f, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _c_f, _c_f, _sz,
+                                         _i, _i, _i, _u, _c_f]),
+}
+# the plan's layout (int32 words): CURL_RAGGED_ALIGN, _STAMP, _HEADER_WORDS, _DESC_WORDS, _MAX_IMAGES
+RAGGED_ALIGN, RAGGED_STAMP, RAGGED_HEADER_WORDS, RAGGED_DESC_WORDS, RAGGED_MAX_IMAGES = 16, 0x52474731, 32, 16, 65535
+
 _lib = None
 
 
@@ -150,7 +163,7 @@ def load():
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
-            list(SIGNATURES_FG.items()):
+            list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -88,6 +88,52 @@ def enhance(net, img_u8, mask_u8, device, view="float", foreground=False):
     return out[0].cpu().numpy()
 
 
+@torch.no_grad()
+def enhance_many(net, images_u8, masks_u8, device, view="pil", batch_size=32):
+    """enhance for a list of images of any sizes: images_u8[i] HxWx3|4 uint8, masks_u8[i] HxW uint8 -> a list of HxWx3 uint8
+    arrays.  Per batch of at most batch_size images: the files' bytes go up into one arena (ops.RaggedBytes.pack), the 320x320
+    views are made per image (ops.encoder_view_u8hwc, or encoder_view for view="float"), the encoder runs ONCE on the
+    concatenated [n,3,320,320] views, and the full-resolution pass of every image is one ragged call
+    (ops.*_u8hwc_ragged).  Given the same coefficients / knots every array equals enhance(net, img, mask, device, view=view) of
+    that image alone, byte for byte; the encoder's convolutions on a batch of n may differ from a batch of one in the last bits
+    (the convolution library's choice of algorithm per batch size, not this path's)."""
+    if view not in ("float", "pil"):
+        raise ValueError(f"view must be 'float' or 'pil', got {view!r}")
+    if len(images_u8) != len(masks_u8):
+        raise ValueError(f"one mask per image: {len(images_u8)} images, {len(masks_u8)} masks")
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    device = torch.device(device)
+    results = []
+    for b0 in range(0, len(images_u8), batch_size):
+        # alpha dropped on the host, as enhance does (the ragged entries would take RGBA as it is; the float view needs RGB)
+        imgs = [np.ascontiguousarray(np.asarray(x)[..., :3]) for x in images_u8[b0:b0 + batch_size]]
+        rb = ops.RaggedBytes.pack(imgs, device)
+        wm = ops.RaggedBytes.pack([np.array(m, dtype=np.uint8) for m in masks_u8[b0:b0 + batch_size]], device)
+        smalls, msmalls = [], []
+        for i in range(len(rb)):
+            rgb, white = rb.image(i)[None], wm.image(i)[None]
+            if view == "pil":
+                small, msmall = ops.encoder_view_u8hwc(rgb, white)
+            else:
+                small, msmall = encoder_view(ops.u8hwc_to_f32chw(rgb), white[:, None].float() / 255.0)
+            smalls.append(small), msmalls.append(msmall)
+        small, msmall = torch.cat(smalls), torch.cat(msmalls)
+        if isinstance(net, model_mod.TriSpaceRegNet):
+            coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)
+            out = ops.trispace_forward_u8hwc_ragged(rb, coeffs, wm)
+        else:
+            knots = net.predict_knots(small * msmall)
+            L, R, H = knots[:, :net.curve_break_1], knots[:, net.curve_break_1:net.curve_break_2], knots[:, net.curve_break_2:]
+            cl = net.curllayer
+            out, _ = ops.curl_layer_forward_u8hwc_ragged(rb, L[:, :cl.num_lab_points].contiguous(), R[:, :cl.num_rgb_points].contiguous(),
+                                                         H[:, :cl.num_hsv_points].contiguous(), wm)
+        host = out.arena.cpu().numpy()  # one download per batch
+        for (h, w), o in zip(out.shapes, out.offsets):
+            results.append(host[o:o + h * w * 3].reshape(h, w, 3).copy())
+    return results
+
+
 def infer(argv=None):
     parser = argparse.ArgumentParser(description="Run image enhancement model on a single image")
     parser.add_argument("--img_path", type=str, required=True, help="Path to image to enhancement")

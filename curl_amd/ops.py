@@ -1038,6 +1038,204 @@ def curl_layer_foreground_u8hwc(img_u8, L, R, H, fg_mask):
     return out, reg
 
 
+# ------------------------------------------------------------------ ragged batches (include/curl_hip_ragged.h)
+_ragged_plans = {}  # (shapes, channels, has_mask, operator, device) -> _RaggedPlan
+_RAGGED_PLANS_KEPT = 16
+
+
+class _RaggedPlan:
+    """One plan of the library's: the host copy (int32), its upload (None for a host-only plan) and what the callers read from
+    it -- the arena sizes and the per-image offsets, from the descriptors as the header documents them."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev = host, dev
+        w = host.numpy()
+        hw, dw = _lib.RAGGED_HEADER_WORDS, _lib.RAGGED_DESC_WORDS
+        B = int(w[1])
+        self.nbytes = host.numel() * 4
+        self.img_bytes, self.mask_bytes, self.out_bytes = (int(v) for v in w[12:18].view("int64"))
+        d = w[hw:hw + B * dw].reshape(B, dw)
+        off = d[:, 10:16].copy().view("int64")  # img_off, mask_off, out_off per descriptor
+        order = d[:, 1].argsort()               # the descriptors are sorted by class: back to image order
+        self.img_off, self.mask_off, self.out_off = ([int(v) for v in off[order, k]] for k in range(3))
+
+
+def _ragged_plan(shapes, channels, has_mask, nc_arg, device):
+    """The plan of a shape list for one operator (nc_arg: the entries' num_coeffs, 0 = the curve layer), built on the host by
+    the library, uploaded once and kept (device None: host only); the oldest of more than sixteen is dropped."""
+    key = (tuple(shapes), tuple(channels), bool(has_mask), nc_arg, device)
+    plan = _ragged_plans.get(key)
+    if plan is None:
+        import numpy as np
+        lib = _lib.load()
+        B = len(shapes)
+        if B > _lib.RAGGED_MAX_IMAGES:
+            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
+        nbytes = lib.curl_ragged_plan_bytes(B, nc_arg)
+        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
+        hs, ws, cs = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes], channels))
+        _lib.check(lib.curl_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, cs.ctypes.data, int(bool(has_mask)), nc_arg,
+                                        host.data_ptr(), nbytes), "curl_ragged_plan")
+        if len(_ragged_plans) >= _RAGGED_PLANS_KEPT:
+            del _ragged_plans[next(iter(_ragged_plans))]
+        plan = _ragged_plans[key] = _RaggedPlan(host, host.to(device) if device is not None else None)
+    return plan
+
+
+class RaggedBytes:
+    """B byte images of different sizes in ONE buffer (the arenas of include/curl_hip_ragged.h): image i's H_i x W_i x C_i
+    bytes start `offsets[i]` bytes into `arena`, every offset a multiple of 16, the images in index order with only the
+    padding that needs.  The same class carries the images (C = 3 | 4), their 'L' masks (C = 1, [H,W]) and the outputs (C = 3).
+    `image(i)[None]` is what ops.encoder_view_u8hwc takes."""
+
+    def __init__(self, arena, shapes, offsets, channels):
+        self.arena, self.shapes, self.offsets, self.channels = arena, list(shapes), list(offsets), list(channels)
+
+    def __len__(self):
+        return len(self.shapes)
+
+    @property
+    def device(self):
+        return self.arena.device
+
+    @staticmethod
+    def layout(shapes, channels):
+        """-> (offsets, arena bytes) of the shape list, from the library's plan.  channels: all 1 (masks), or 3 | 4 per image."""
+        shapes, channels = [(int(h), int(w)) for h, w in shapes], [int(c) for c in channels]
+        if not shapes:
+            return [], 0
+        for (h, w), c in zip(shapes, channels):
+            if h <= 0 or w <= 0:
+                raise ValueError(f"an image of a ragged batch has a zero dimension: {(h, w)}")
+        masks = all(c == 1 for c in channels)
+        if not masks and any(c not in (3, 4) for c in channels):
+            raise ValueError(f"the images of a ragged batch are uint8 [H,W,3|4] (masks: all [H,W]), got channels {channels}")
+        plan = _ragged_plan(shapes, [3] * len(shapes) if masks else channels, masks, 0, None)
+        return (plan.mask_off, plan.mask_bytes) if masks else (plan.img_off, plan.img_bytes)
+
+    @classmethod
+    def pack(cls, images, device=None):
+        """A list of uint8 [H,W,3|4] images (or of [H,W] masks), numpy arrays or tensors on the host or the device, each
+        copied straight into its slice of one arena on `device` (None: the first tensor's device, else the host)."""
+        import numpy as np
+        ts = []
+        for k, x in enumerate(images):
+            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+            if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (3, 4)):
+                raise ValueError(f"image {k} of a ragged batch must be uint8 [H,W,3|4] (a mask: [H,W]), got {t.dtype} {tuple(t.shape)}")
+            if t.numel() == 0:
+                raise ValueError(f"image {k} of a ragged batch has a zero dimension: {tuple(t.shape)}")
+            ts.append(t)
+        if len({t.dim() for t in ts}) > 1:
+            raise ValueError("a ragged batch holds images ([H,W,3|4]) or masks ([H,W]), not both")
+        if device is None:
+            device = ts[0].device if ts else torch.device("cpu")
+        shapes, channels = [tuple(t.shape[:2]) for t in ts], [t.shape[2] if t.dim() == 3 else 1 for t in ts]
+        offsets, nbytes = cls.layout(shapes, channels)
+        rb = cls(torch.empty(nbytes, dtype=torch.uint8, device=device), shapes, offsets, channels)
+        for i, t in enumerate(ts):
+            rb.image(i).copy_(t)
+        return rb
+
+    def image(self, i):
+        """A view of image i: [H,W,C] (masks: [H,W])."""
+        (h, w), c, o = self.shapes[i], self.channels[i], self.offsets[i]
+        flat = self.arena[o:o + h * w * c]
+        return flat.view(h, w) if c == 1 else flat.view(h, w, c)
+
+    def images(self):
+        return [self.image(i) for i in range(len(self))]
+
+
+def _ragged_inputs(images, white_masks, device):
+    """The two arenas of a ragged call, checked -> (images, masks or None)."""
+    if not isinstance(images, RaggedBytes):  # a list: to the device its tensors are on, else to the coefficients' / knots'
+        images = list(images)
+        device = next((t.device for t in images if isinstance(t, torch.Tensor) and t.is_cuda), device)
+    rb = images if isinstance(images, RaggedBytes) else RaggedBytes.pack(images, device)
+    if any(c not in (3, 4) for c in rb.channels):
+        raise ValueError("images must be uint8 [H,W,3|4]")
+    _need_device(rb.arena, "images")
+    wm = None
+    if white_masks is not None:
+        n = len(white_masks)
+        if n != len(rb):
+            raise ValueError(f"white_masks must hold one mask per image ({len(rb)}), got {n}")
+        wm = white_masks if isinstance(white_masks, RaggedBytes) else RaggedBytes.pack(list(white_masks), rb.device)
+        if any(c != 1 for c in wm.channels) or wm.shapes != rb.shapes:
+            raise ValueError(f"white_masks must be uint8 [H,W] masks of the images' sizes {rb.shapes}, got {wm.shapes}")
+    _need_device(rb.arena, "images")
+    if wm is not None:
+        _need_device(wm.arena, "white_masks")
+        _check_same_device([("images", rb.arena), ("white_masks", wm.arena)])
+    return rb, wm
+
+
+def _ragged_arenas(rb, wm, nc_arg):
+    """The plan of the call and its out arena; the callers' arenas are held to the plan's layout."""
+    plan = _ragged_plan(rb.shapes, rb.channels, wm is not None, nc_arg, rb.device)
+    if rb.offsets != plan.img_off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    out = RaggedBytes(torch.empty(plan.out_bytes, dtype=torch.uint8, device=rb.device), rb.shapes, plan.out_off, [3] * len(rb))
+    return plan, out
+
+
+def _ragged_empty(images, device):
+    if isinstance(images, RaggedBytes):
+        return len(images) == 0, images.device
+    return len(images) == 0, device
+
+
+def trispace_forward_u8hwc_ragged(images, coeffs, white_masks=None):
+    """trispace_forward_u8hwc for a batch of images of different sizes in one launch per class of images (dword / byte):
+    images a RaggedBytes or a list of uint8 [H,W,3|4] (alpha is not read), coeffs [B,3,3,n], white_masks None or one [H,W]
+    uint8 mask per image (a RaggedBytes or a list).  -> RaggedBytes of the [H,W,3] outputs; every image's bytes equal
+    trispace_forward_u8hwc of that image alone."""
+    empty, device = _ragged_empty(images, coeffs.device if isinstance(coeffs, torch.Tensor) else None)
+    if empty:
+        return RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], [])
+    lib = _lib.load()
+    rb, wm = _ragged_inputs(images, white_masks, device)
+    _check_coeffs(coeffs, len(rb))
+    _check_same_device([("images", rb.arena), ("coeffs", coeffs)])
+    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
+    nc = _nc_arg(c.shape[3])
+    plan, out = _ragged_arenas(rb, wm, nc)
+    with torch.cuda.device(rb.device):
+        rc = lib.curl_trispace_fwd_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), c.data_ptr(), _ptr(wm.arena if wm is not None else None),
+                                                wm.arena.numel() if wm else 0, out.arena.data_ptr(), out.arena.numel(),
+                                                plan.host.data_ptr(), plan.dev.data_ptr(), plan.nbytes, nc, 0, _stream(rb.arena))
+    _lib.check(rc, "curl_trispace_fwd_ragged_u8hwc")
+    return out
+
+
+def curl_layer_forward_u8hwc_ragged(images, L, R, H, white_masks=None):
+    """curl_layer_forward_u8hwc(img, None, L, R, H, white_mask) for a batch of images of different sizes: one curve collapse
+    for the B knot rows and one launch per class of images.  -> (RaggedBytes of the [H,W,3] outputs, reg [B]); bytes and reg
+    equal the single-image calls'."""
+    empty, device = _ragged_empty(images, L.device if isinstance(L, torch.Tensor) else None)
+    if empty:
+        return (RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], []),
+                torch.zeros(0, dtype=torch.float32, device=device))
+    lib = _lib.load()
+    rb, wm = _ragged_inputs(images, white_masks, device)
+    B = len(rb)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
+    _check_same_device([("images", rb.arena), ("L", Lc), ("R", Rc), ("H", Hc)])
+    plan, out = _ragged_arenas(rb, wm, 0)
+    reg = torch.empty(B, dtype=torch.float32, device=rb.device)
+    ws, nbytes = _workspace(B, n_knots, rb.device)
+    with torch.cuda.device(rb.device):
+        rc = lib.curl_layer_fwd_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
+                                             _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm else 0, out.arena.data_ptr(),
+                                             out.arena.numel(), reg.data_ptr(), ws.data_ptr(), nbytes, plan.host.data_ptr(),
+                                             plan.dev.data_ptr(), plan.nbytes, Kl, Kr, Kh, 0, _stream(rb.arena))
+    _lib.check(rc, "curl_layer_fwd_ragged_u8hwc")
+    return out, reg
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
