@@ -140,6 +140,17 @@ SIGNATURES_RAGGED = {
 # the plan's layout (int32 words): CURL_RAGGED_ALIGN, _STAMP, _HEADER_WORDS, _DESC_WORDS, _MAX_IMAGES
 RAGGED_ALIGN, RAGGED_STAMP, RAGGED_HEADER_WORDS, RAGGED_DESC_WORDS, RAGGED_MAX_IMAGES = 16, 0x52474731, 32, 16, 65535
 
+# include/curl_hip_view_ragged.h: the encoder's views of a batch of images of different sizes in one launch (a sixth table,
+# for the same reason -- tests/test_encoder_view_abi.py holds SIGNATURES_VIEW to the three entries of curl_hip_view.h; the plan
+# functions take and fill HOST memory and make no HIP call)
+SIGNATURES_VIEW_RAGGED = {
+    "curl_encoder_view_ragged_plan_bytes": (_sz, [_i, _c_f, _c_f, _i]),
+    "curl_encoder_view_ragged_plan": (_i, [_i, _c_f, _c_f, _c_f, _i, _i, _c_f, _sz]),
+    "curl_encoder_view_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _c_f, _c_f, _i, _u, _c_f]),
+}
+# the plan's layout (int32 words): CURL_VIEW_RAGGED_STAMP, _HEADER_WORDS, _DESC_WORDS, _MAX_IMAGES
+VIEW_RAGGED_STAMP, VIEW_RAGGED_HEADER_WORDS, VIEW_RAGGED_DESC_WORDS, VIEW_RAGGED_MAX_IMAGES = 0x52565031, 32, 32, 65535
+
 _lib = None
 
 
@@ -163,7 +174,7 @@ def load():
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
-            list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()):
+            list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

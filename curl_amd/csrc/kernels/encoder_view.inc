@@ -9,6 +9,7 @@
 //   3. runs the VERTICAL pass over those rounded bytes, converts and stores: consecutive lanes, consecutive floats of a row.
 // Every index that comes out of the plan is clamped to the window, and the window to the image by the call's own H and W:
 // a foreign plan gives wrong values, never an access outside the tensors or the workgroup's LDS.
+// Steps 1 - 3 are view_tile, which encoder_view_ragged_kernel (encoder_view_ragged.inc) runs too.
 // (the kernel takes these one by one -- pointers and ints -- and derives the last four itself: view_layout)
 struct ViewArgs {
   const uint8_t* img;
@@ -35,6 +36,9 @@ __host__ __device__ static inline void view_layout(ViewArgs& a) {
   a.off_h = a.off_ky + 4u * (unsigned)(a.tr * view_lds_row(a.ksy));
   a.off_stage = a.off_h + 4u * (unsigned)(a.nrows_cap << a.tc_log2);
 }
+__host__ __device__ static inline unsigned view_lds_bytes(const ViewArgs& a) {
+  return a.off_stage + (unsigned)a.chunk_rows * (unsigned)(a.pitch_img + a.pitch_mask);
+}
 
 // len bytes from g to the LDS dwords at dst, laid out from g's 4-byte boundary below: byte i of the segment lands at LDS byte
 // ((uintptr_t)g & 3) + i.  One wavefront per call; a dword that the segment does not cover whole is put together from its bytes.
@@ -59,43 +63,33 @@ __device__ __forceinline__ int view_clampi(int v, int lo, int hi) { return min(m
 // first + count - origin of table entries that may hold anything: wrapping, never overflowing
 __device__ __forceinline__ int view_span(int first, int count, int origin) { return (int)((unsigned)first + (unsigned)count - (unsigned)origin); }
 
-__global__ __launch_bounds__(256) void encoder_view_kernel(const uint8_t* img, const uint8_t* mask, const int* plan, float* view, float* mask_view,
-                                                           int H, int W, int size, int C, int ksx, int ksy, int tc_log2, int tr, int ncols_cap,
-                                                           int nrows_cap, int chunk_rows, int pitch_img, int pitch_mask) {
-  ViewArgs a = {img, mask, plan, view, mask_view, H, W, size, C, ksx, ksy, tc_log2, tr, ncols_cap, nrows_cap, chunk_rows, pitch_img, pitch_mask, 0, 0u, 0u, 0u};
-  view_layout(a);
-  extern __shared__ __align__(16) unsigned char view_lds[];
+// A workgroup's tile of a view: its first output column and row, and how many of each lie inside the view
+struct ViewTile {
+  int c0, r0, nc, nr;
+};
+__device__ __forceinline__ ViewTile view_tile_of(const ViewArgs& a, int tile) {
+  const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+  const int c0 = tx << a.tc_log2, r0 = ty * a.tr;
+  return ViewTile{c0, r0, min(1 << a.tc_log2, a.size - c0), min(a.tr, a.size - r0)};
+}
+
+// Steps 1 - 3 for ONE tile of ONE image: the code of both kernels (one copy: the shared arithmetic is what makes their bits
+// equal).  a: the image's numbers, laid out (view_layout); view_lds: the workgroup's LDS, view_lds_bytes(a) of it; plan_x: the
+// image's two tables (`size` X rows, then `size` Y rows); img_b / mask_b: the image's first byte (mask_b nullable); vout / mout:
+// the image's [3,size,size] / [1,size,size] (mout nullable).  Every thread of the workgroup calls it (barriers inside).
+__device__ __forceinline__ void view_tile(const ViewArgs& a, unsigned char* view_lds, const int* plan_x, const uint8_t* img_b, const uint8_t* mask_b,
+                                          float* vout, float* mout, const ViewTile& tile) {
   int* const kx = reinterpret_cast<int*>(view_lds);
   int* const ky = reinterpret_cast<int*>(view_lds + a.off_ky);
   unsigned* const hbuf = reinterpret_cast<unsigned*>(view_lds + a.off_h);
   unsigned char* const stage = view_lds + a.off_stage;
-
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int S = a.size, TC = 1 << a.tc_log2, b = (int)blockIdx.y;
-  const int tx = (int)blockIdx.x % a.tiles_x, ty = (int)blockIdx.x / a.tiles_x;
-  const int c0 = tx << a.tc_log2, r0 = ty * a.tr;
-  const int nc = min(TC, S - c0), nr = min(a.tr, S - r0);
-  float* const vout = a.view + (size_t)b * 3u * (size_t)S * (size_t)S;
-  float* const mout = a.mask_view ? a.mask_view + (size_t)b * (size_t)S * (size_t)S : nullptr;
+  const int S = a.size, TC = 1 << a.tc_log2, C = a.C;
+  const int c0 = tile.c0, r0 = tile.r0, nc = tile.nc, nr = tile.nr;
   const size_t plane = (size_t)S * (size_t)S;
-
-  // a plan made for another shape: say so in every value (as the layer backward answers an unprepared workspace row)
-  const ViewHeader* const hdr = reinterpret_cast<const ViewHeader*>(a.plan);
-  if (hdr->stamp != kViewStamp || hdr->H != a.H || hdr->W != a.W || hdr->size != S) {
-    const float nan = __builtin_nanf("");
-    for (int i = t; i < (nr << a.tc_log2); i += 256) {
-      const int c = i & (TC - 1), r = i >> a.tc_log2;
-      if (c >= nc) continue;
-      const size_t o = (size_t)(r0 + r) * (size_t)S + (size_t)(c0 + c);
-      vout[o] = nan, vout[plane + o] = nan, vout[2 * plane + o] = nan;
-      if (mout) mout[o] = nan;
-    }
-    return;
-  }
 
   // 1. the tile's table rows: a wavefront per row
   const int rix = view_row_ints(a.ksx), riy = view_row_ints(a.ksy), lsx = view_lds_row(a.ksx), lsy = view_lds_row(a.ksy);
-  const int* const plan_x = a.plan + kViewHeaderInts;
   const int* const plan_y = plan_x + (size_t)S * (size_t)rix;
   for (int c = wave; c < nc; c += 4)
     for (int j = lane; j < rix; j += 64) kx[c * lsx + j] = plan_x[(size_t)(c0 + c) * (size_t)rix + j];
@@ -108,8 +102,6 @@ __global__ __launch_bounds__(256) void encoder_view_kernel(const uint8_t* img, c
   const int wy0 = view_clampi(ky[0], 0, a.H - 1);
   const int nrows = view_clampi(view_span(ky[(nr - 1) * lsy], ky[(nr - 1) * lsy + 1], wy0), 1, min(a.nrows_cap, a.H - wy0));
 
-  const uint8_t* const img_b = a.img + (size_t)b * (size_t)a.H * (size_t)a.W * (size_t)C;
-  const uint8_t* const mask_b = a.mask ? a.mask + (size_t)b * (size_t)a.H * (size_t)a.W : nullptr;
   unsigned char* const mstage = stage + (size_t)a.chunk_rows * (size_t)a.pitch_img;
 
   // 2. chunks of input rows: stage, then the horizontal pass
@@ -157,4 +149,37 @@ __global__ __launch_bounds__(256) void encoder_view_kernel(const uint8_t* img, c
     vout[o] = view_unit(view_clip(s0)), vout[plane + o] = view_unit(view_clip(s1)), vout[2 * plane + o] = view_unit(view_clip(s2));
     if (mout) mout[o] = view_mask(view_clip(sm));
   }
+}
+
+__global__ __launch_bounds__(256) void encoder_view_kernel(const uint8_t* img, const uint8_t* mask, const int* plan, float* view, float* mask_view,
+                                                           int H, int W, int size, int C, int ksx, int ksy, int tc_log2, int tr, int ncols_cap,
+                                                           int nrows_cap, int chunk_rows, int pitch_img, int pitch_mask) {
+  ViewArgs a = {img, mask, plan, view, mask_view, H, W, size, C, ksx, ksy, tc_log2, tr, ncols_cap, nrows_cap, chunk_rows, pitch_img, pitch_mask, 0, 0u, 0u, 0u};
+  view_layout(a);
+  extern __shared__ __align__(16) unsigned char view_lds[];
+
+  const int t = (int)threadIdx.x;
+  const int S = a.size, TC = 1 << a.tc_log2, b = (int)blockIdx.y;
+  const ViewTile tile = view_tile_of(a, (int)blockIdx.x);
+  float* const vout = a.view + (size_t)b * 3u * (size_t)S * (size_t)S;
+  float* const mout = a.mask_view ? a.mask_view + (size_t)b * (size_t)S * (size_t)S : nullptr;
+  const size_t plane = (size_t)S * (size_t)S;
+
+  // a plan made for another shape: say so in every value (as the layer backward answers an unprepared workspace row)
+  const ViewHeader* const hdr = reinterpret_cast<const ViewHeader*>(a.plan);
+  if (hdr->stamp != kViewStamp || hdr->H != a.H || hdr->W != a.W || hdr->size != S) {
+    const float nan = __builtin_nanf("");
+    for (int i = t; i < (tile.nr << a.tc_log2); i += 256) {
+      const int c = i & (TC - 1), r = i >> a.tc_log2;
+      if (c >= tile.nc) continue;
+      const size_t o = (size_t)(tile.r0 + r) * (size_t)S + (size_t)(tile.c0 + c);
+      vout[o] = nan, vout[plane + o] = nan, vout[2 * plane + o] = nan;
+      if (mout) mout[o] = nan;
+    }
+    return;
+  }
+
+  const uint8_t* const img_b = a.img + (size_t)b * (size_t)a.H * (size_t)a.W * (size_t)C;
+  const uint8_t* const mask_b = a.mask ? a.mask + (size_t)b * (size_t)a.H * (size_t)a.W : nullptr;
+  view_tile(a, view_lds, a.plan + kViewHeaderInts, img_b, mask_b, vout, mout, tile);
 }

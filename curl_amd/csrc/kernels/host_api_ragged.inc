@@ -26,6 +26,20 @@ static uint64_t ragged_hash_word(uint64_t h, uint32_t w) {  // FNV-1a, a byte at
   for (int k = 0; k < 4; ++k) h = (h ^ ((w >> (8 * k)) & 0xffu)) * 1099511628211ull;
   return h;
 }
+// The arenas' layout, the one rule of every plan over a ragged batch (this file's and the encoder view's, host_api_view.inc):
+// the images in index order, each offset rounded up to kRaggedAlign.  place() gives image i its three offsets and moves on;
+// afterwards img / mask / out are the arena sizes.
+struct RaggedArenas {
+  uint64_t img = 0, mask = 0, out = 0;
+  int place(uint64_t px, int channels, bool has_mask, uint64_t& img_off, uint64_t& mask_off, uint64_t& out_off) {
+    const auto align = [](uint64_t v) { return (v + kRaggedAlign - 1) & ~(kRaggedAlign - 1); };
+    img = align(img), out = align(out), mask = align(mask);
+    img_off = img, out_off = out, mask_off = has_mask ? mask : 0;
+    img += px * (uint64_t)channels, out += px * 3u, mask += has_mask ? px : 0;
+    if ((img | out | mask) >> 63) return fail(CURL_E_SHAPE, "ragged batch: an arena exceeds 2^63 bytes");
+    return 0;
+  }
+};
 static bool ragged_is_dword(const RaggedOp& op, int H, int W) { return op.rows ? W % 4 == 0 : ((uint64_t)H * (uint64_t)W) % 4 == 0; }
 
 // Row tiles of a whole launch: the block size is one per launch.  row_blocks' rule for one image -- among 64 / 128 / 192 /
@@ -66,9 +80,9 @@ static int ragged_build(int B, const int* H, const int* W, const int* C, bool ha
   const unsigned threads[2] = {op.rows ? ragged_row_threads(B, H, W, op, true) : 256u,
                                op.rows ? ragged_row_threads(B, H, W, op, false) : 256u};
   memset(p, 0, ragged_plan_words(B) * sizeof(int));
-  uint64_t off_img = 0, off_mask = 0, off_out = 0, grid[2] = {0, 0};
+  uint64_t grid[2] = {0, 0};
+  RaggedArenas arenas;
   int cursor[2] = {0, n_dword};
-  const auto align = [](uint64_t v) { return (v + kRaggedAlign - 1) & ~(kRaggedAlign - 1); };
   for (int i = 0; i < B; ++i) {
     const int cls = ragged_is_dword(op, H[i], W[i]) ? 0 : 1;
     const unsigned vec = cls == 0 ? 4u : 1u;
@@ -80,16 +94,15 @@ static int ragged_build(int B, const int* H, const int* W, const int* C, bool ha
     d[RD_FIRST] = (int)grid[cls], d[RD_INDEX] = i, d[RD_H] = H[i], d[RD_W] = W[i], d[RD_CHANNELS] = C[i], d[RD_N] = (int)n;
     d[RD_UNITS] = (int)units, d[RD_SEGS] = (int)segs, d[RD_TILES] = (int)tiles;
     grid[cls] += tiles;
-    off_img = align(off_img), off_out = align(off_out), off_mask = align(off_mask);
-    put64(d + RD_IMG_OFF, off_img), put64(d + RD_OUT_OFF, off_out), put64(d + RD_MASK_OFF, has_mask ? off_mask : 0);
-    off_img += px * (uint64_t)C[i], off_out += px * 3u, off_mask += has_mask ? px : 0;
-    if ((off_img | off_out | off_mask) >> 63) return fail(CURL_E_SHAPE, "ragged batch: an arena exceeds 2^63 bytes");
+    uint64_t off_img, off_mask, off_out;
+    if (int rc = arenas.place(px, C[i], has_mask, off_img, off_mask, off_out)) return rc;
+    put64(d + RD_IMG_OFF, off_img), put64(d + RD_OUT_OFF, off_out), put64(d + RD_MASK_OFF, off_mask);
   }
   p[RH_STAMP] = (int)kRaggedStamp, p[RH_B] = B, p[RH_OP] = op.count, p[RH_HAS_MASK] = has_mask;
   p[RH_LAUNCHES] = (n_dword > 0) + (n_dword < B), p[RH_N_DWORD] = n_dword, p[RH_N_BYTE] = B - n_dword;
   p[RH_THREADS_DWORD] = n_dword > 0 ? (int)threads[0] : 0, p[RH_GRID_DWORD] = (int)grid[0];
   p[RH_THREADS_BYTE] = n_dword < B ? (int)threads[1] : 0, p[RH_GRID_BYTE] = (int)grid[1];
-  put64(p + RH_IMG_BYTES, off_img), put64(p + RH_MASK_BYTES, off_mask), put64(p + RH_OUT_BYTES, off_out), put64(p + RH_HASH, hash);
+  put64(p + RH_IMG_BYTES, arenas.img), put64(p + RH_MASK_BYTES, arenas.mask), put64(p + RH_OUT_BYTES, arenas.out), put64(p + RH_HASH, hash);
   return 0;
 }
 

@@ -92,8 +92,8 @@ def enhance(net, img_u8, mask_u8, device, view="float", foreground=False):
 def enhance_many(net, images_u8, masks_u8, device, view="pil", batch_size=32):
     """enhance for a list of images of any sizes: images_u8[i] HxWx3|4 uint8, masks_u8[i] HxW uint8 -> a list of HxWx3 uint8
     arrays.  Per batch of at most batch_size images: the files' bytes go up into one arena (ops.RaggedBytes.pack), the 320x320
-    views are made per image (ops.encoder_view_u8hwc, or encoder_view for view="float"), the encoder runs ONCE on the
-    concatenated [n,3,320,320] views, and the full-resolution pass of every image is one ragged call
+    views of all of them are made in one launch (ops.encoder_view_u8hwc_ragged; view="float": per image, encoder_view), the
+    encoder runs ONCE on the [n,3,320,320] views, and the full-resolution pass of every image is one ragged call
     (ops.*_u8hwc_ragged).  Given the same coefficients / knots every array equals enhance(net, img, mask, device, view=view) of
     that image alone, byte for byte; the encoder's convolutions on a batch of n may differ from a batch of one in the last bits
     (the convolution library's choice of algorithm per batch size, not this path's)."""
@@ -106,19 +106,20 @@ def enhance_many(net, images_u8, masks_u8, device, view="pil", batch_size=32):
     device = torch.device(device)
     results = []
     for b0 in range(0, len(images_u8), batch_size):
-        # alpha dropped on the host, as enhance does (the ragged entries would take RGBA as it is; the float view needs RGB)
-        imgs = [np.ascontiguousarray(np.asarray(x)[..., :3]) for x in images_u8[b0:b0 + batch_size]]
+        # view="pil": the images go up with the channel count the files have (both ragged entries take RGBA as it is);
+        # view="float": alpha dropped on the host, as enhance does (the float view needs RGB)
+        imgs = [np.ascontiguousarray(np.asarray(x)[..., :4 if view == "pil" else 3]) for x in images_u8[b0:b0 + batch_size]]
         rb = ops.RaggedBytes.pack(imgs, device)
         wm = ops.RaggedBytes.pack([np.array(m, dtype=np.uint8) for m in masks_u8[b0:b0 + batch_size]], device)
-        smalls, msmalls = [], []
-        for i in range(len(rb)):
-            rgb, white = rb.image(i)[None], wm.image(i)[None]
-            if view == "pil":
-                small, msmall = ops.encoder_view_u8hwc(rgb, white)
-            else:
+        if view == "pil":
+            small, msmall = ops.encoder_view_u8hwc_ragged(rb, wm)  # every image's view in one launch
+        else:
+            smalls, msmalls = [], []
+            for i in range(len(rb)):
+                rgb, white = rb.image(i)[None], wm.image(i)[None]
                 small, msmall = encoder_view(ops.u8hwc_to_f32chw(rgb), white[:, None].float() / 255.0)
-            smalls.append(small), msmalls.append(msmall)
-        small, msmall = torch.cat(smalls), torch.cat(msmalls)
+                smalls.append(small), msmalls.append(msmall)
+            small, msmall = torch.cat(smalls), torch.cat(msmalls)
         if isinstance(net, model_mod.TriSpaceRegNet):
             coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)
             out = ops.trispace_forward_u8hwc_ragged(rb, coeffs, wm)

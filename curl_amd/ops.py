@@ -1286,6 +1286,84 @@ def encoder_view_u8hwc(img_u8, mask_u8=None, size=_lib.VIEW_SIZE_DEFAULT):
     return view, mview
 
 
+# ------------------------------------------------------------------ the views of a ragged batch (include/curl_hip_view_ragged.h)
+_view_ragged_plans = {}  # (shapes, channels, has_mask, size, device) -> _ViewRaggedPlan
+_VIEW_RAGGED_PLANS_KEPT = 16
+
+
+class _ViewRaggedPlan:
+    """One plan of the library's: the host copy (int32), its upload and what the caller reads from it -- the arena sizes and
+    the per-image offsets, from the descriptors as the header documents them."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev = host, dev
+        w = host.numpy()
+        hw, dw = _lib.VIEW_RAGGED_HEADER_WORDS, _lib.VIEW_RAGGED_DESC_WORDS
+        B = int(w[1])
+        self.nbytes = host.numel() * 4
+        self.img_bytes, self.mask_bytes = (int(v) for v in w[8:12].view("int64"))
+        off = w[hw:hw + B * dw].reshape(B, dw)[:, 20:24].copy().view("int64")  # img_off, mask_off per descriptor (index order)
+        self.img_off, self.mask_off = ([int(v) for v in off[:, k]] for k in range(2))
+
+
+def _view_ragged_plan(shapes, channels, has_mask, size, device):
+    """The plan of a shape list at one size, built on the host by the library, uploaded once and kept; the oldest of more than
+    sixteen is dropped."""
+    key = (tuple(shapes), tuple(channels), bool(has_mask), size, device)
+    plan = _view_ragged_plans.get(key)
+    if plan is None:
+        import numpy as np
+        lib = _lib.load()
+        B = len(shapes)
+        if B > _lib.VIEW_RAGGED_MAX_IMAGES:
+            raise ValueError(f"a ragged batch holds at most {_lib.VIEW_RAGGED_MAX_IMAGES} images, got {B}")
+        hs, ws, cs = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes], channels))
+        nbytes = lib.curl_encoder_view_ragged_plan_bytes(B, hs.ctypes.data, ws.ctypes.data, size)
+        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
+        _lib.check(lib.curl_encoder_view_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, cs.ctypes.data, int(bool(has_mask)), size,
+                                                     host.data_ptr(), nbytes), "curl_encoder_view_ragged_plan")
+        if len(_view_ragged_plans) >= _VIEW_RAGGED_PLANS_KEPT:
+            del _view_ragged_plans[next(iter(_view_ragged_plans))]
+        plan = _view_ragged_plans[key] = _ViewRaggedPlan(host, host.to(device))
+    return plan
+
+
+def encoder_view_u8hwc_ragged(images, masks=None, size=_lib.VIEW_SIZE_DEFAULT):
+    """encoder_view_u8hwc for a batch of images of different sizes in ONE launch: images a RaggedBytes or a list of uint8
+    [H,W,3|4] (alpha is not read), masks None or one [H,W] uint8 mask per image (a RaggedBytes or a list).
+    -> (view float32 [B,3,size,size], mask_view float32 [B,1,size,size] or None); image i's view equals encoder_view_u8hwc of
+    that image alone, bit for bit.  The arenas are the ones the *_u8hwc_ragged ops take."""
+    size = int(size)
+    empty, device = _ragged_empty(images, None)
+    if empty:
+        return (torch.empty(0, 3, size, size, dtype=torch.float32, device=device),
+                None if masks is None else torch.empty(0, 1, size, size, dtype=torch.float32, device=device))
+    lib = _lib.load()
+    if masks is not None:  # (before anything is packed or uploaded; _ragged_inputs holds the packed arenas to the same)
+        def sizes(x):
+            return [tuple(s) for s in x.shapes] if isinstance(x, RaggedBytes) else [tuple(t.shape) for t in x]
+        want, got = [s[:2] for s in sizes(images)], sizes(masks)
+        if len(got) != len(want):
+            raise ValueError(f"masks must hold one mask per image ({len(want)}), got {len(got)}")
+        if got != want:
+            raise ValueError(f"masks must be uint8 [H,W] masks of the images' sizes {want}, got {got}")
+    rb, wm = _ragged_inputs(images, masks, device)
+    plan = _view_ragged_plan(rb.shapes, rb.channels, wm is not None, size, rb.device)
+    if rb.offsets != plan.img_off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    B = len(rb)
+    view = torch.empty(B, 3, size, size, dtype=torch.float32, device=rb.device)
+    mview = torch.empty(B, 1, size, size, dtype=torch.float32, device=rb.device) if wm is not None else None
+    with torch.cuda.device(rb.device):
+        rc = lib.curl_encoder_view_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), _ptr(wm.arena if wm is not None else None),
+                                                wm.arena.numel() if wm is not None else 0, plan.host.data_ptr(), plan.dev.data_ptr(),
+                                                plan.nbytes, view.data_ptr(), _ptr(mview), size, 0, _stream(rb.arena))
+    _lib.check(rc, "curl_encoder_view_ragged_u8hwc")
+    return view, mview
+
+
 def _planes(t, name):
     _need_device(t, name)
     if t.dim() != 4 or t.dtype != torch.float32:
