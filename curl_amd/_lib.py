@@ -151,6 +151,13 @@ SIGNATURES_VIEW_RAGGED = {
 # the plan's layout (int32 words): CURL_VIEW_RAGGED_STAMP, _HEADER_WORDS, _DESC_WORDS, _MAX_IMAGES
 VIEW_RAGGED_STAMP, VIEW_RAGGED_HEADER_WORDS, VIEW_RAGGED_DESC_WORDS, VIEW_RAGGED_MAX_IMAGES = 0x52565031, 32, 32, 65535
 
+# include/curl_hip_ragged_fg.h: the ragged byte paths, foreground-aware (a seventh table, for the same reason --
+# tests/test_ragged_abi.py holds SIGNATURES_RAGGED to the five entries of curl_hip_ragged.h; the argument lists are the siblings')
+SIGNATURES_RAGGED_FG = {
+    "curl_trispace_fwd_ragged_fg_u8hwc": (_i, list(SIGNATURES_RAGGED["curl_trispace_fwd_ragged_u8hwc"][1])),
+    "curl_layer_fwd_ragged_fg_u8hwc": (_i, list(SIGNATURES_RAGGED["curl_layer_fwd_ragged_u8hwc"][1])),
+}
+
 _lib = None
 
 
@@ -174,7 +181,8 @@ def load():
             "There is no CPU fallback for this path.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
-            list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()):
+            list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()) + \
+            list(SIGNATURES_RAGGED_FG.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -746,7 +746,8 @@ extern "C" {
 // 0.1.13: polynomial orders 1-3: the curl_trispace_fwd_* entries take the order in the high half of num_coeffs and
 //         curl_poly_layer_f32 the degree in the high half of num_variables (include/curl_hip_poly.h)
 // 0.1.16: the ragged byte entries: a batch of images of different sizes in one launch per class (include/curl_hip_ragged.h)
-int curl_version(void) { return 117; }
+// 0.1.18: the ragged byte entries, foreground-aware: dead wavefronts store white unread (include/curl_hip_ragged_fg.h)
+int curl_version(void) { return 118; }
 
 const char* curl_last_error(void) { return g_err; }
 

@@ -97,20 +97,8 @@ def enhance_many(net, images_u8, masks_u8, device, view="pil", batch_size=32):
     (ops.*_u8hwc_ragged).  Given the same coefficients / knots every array equals enhance(net, img, mask, device, view=view) of
     that image alone, byte for byte; the encoder's convolutions on a batch of n may differ from a batch of one in the last bits
     (the convolution library's choice of algorithm per batch size, not this path's)."""
-    if view not in ("float", "pil"):
-        raise ValueError(f"view must be 'float' or 'pil', got {view!r}")
-    if len(images_u8) != len(masks_u8):
-        raise ValueError(f"one mask per image: {len(images_u8)} images, {len(masks_u8)} masks")
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be positive, got {batch_size}")
-    device = torch.device(device)
     results = []
-    for b0 in range(0, len(images_u8), batch_size):
-        # view="pil": the images go up with the channel count the files have (both ragged entries take RGBA as it is);
-        # view="float": alpha dropped on the host, as enhance does (the float view needs RGB)
-        imgs = [np.ascontiguousarray(np.asarray(x)[..., :4 if view == "pil" else 3]) for x in images_u8[b0:b0 + batch_size]]
-        rb = ops.RaggedBytes.pack(imgs, device)
-        wm = ops.RaggedBytes.pack([np.array(m, dtype=np.uint8) for m in masks_u8[b0:b0 + batch_size]], device)
+    for rb, wm in _packed_batches(images_u8, masks_u8, device, view, batch_size):
         if view == "pil":
             small, msmall = ops.encoder_view_u8hwc_ragged(rb, wm)  # every image's view in one launch
         else:
@@ -120,19 +108,62 @@ def enhance_many(net, images_u8, masks_u8, device, view="pil", batch_size=32):
                 small, msmall = encoder_view(ops.u8hwc_to_f32chw(rgb), white[:, None].float() / 255.0)
                 smalls.append(small), msmalls.append(msmall)
             small, msmall = torch.cat(smalls), torch.cat(msmalls)
-        if isinstance(net, model_mod.TriSpaceRegNet):
-            coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)
-            out = ops.trispace_forward_u8hwc_ragged(rb, coeffs, wm)
-        else:
-            knots = net.predict_knots(small * msmall)
-            L, R, H = knots[:, :net.curve_break_1], knots[:, net.curve_break_1:net.curve_break_2], knots[:, net.curve_break_2:]
-            cl = net.curllayer
-            out, _ = ops.curl_layer_forward_u8hwc_ragged(rb, L[:, :cl.num_lab_points].contiguous(), R[:, :cl.num_rgb_points].contiguous(),
-                                                         H[:, :cl.num_hsv_points].contiguous(), wm)
-        host = out.arena.cpu().numpy()  # one download per batch
-        for (h, w), o in zip(out.shapes, out.offsets):
-            results.append(host[o:o + h * w * 3].reshape(h, w, 3).copy())
+        results += _full_resolution_many(net, rb, wm, small, msmall, foreground=False)
     return results
+
+
+@torch.no_grad()
+def enhance_many_foreground(net, images_u8, masks_u8, device, view="pil", batch_size=32):
+    """enhance_many for masks that are segmentation masks: the same contract and the same arrays, byte for byte, but the
+    full-resolution pass of every batch is the foreground ragged call (ops.*_foreground_u8hwc_ragged): wavefronts the white
+    background overwrites entirely never read their pixels, workgroups of such wavefronts stage no table.  The views are made
+    from the whole images, as enhance_many makes them (the encoder sees what it saw)."""
+    results = []
+    for rb, wm in _packed_batches(images_u8, masks_u8, device, view, batch_size):
+        if view == "pil":
+            small, msmall = ops.encoder_view_u8hwc_ragged(rb, wm)
+        else:
+            views = [encoder_view(ops.u8hwc_to_f32chw(rb.image(i)[None]), wm.image(i)[None, None].float() / 255.0) for i in range(len(rb))]
+            small, msmall = torch.cat([v[0] for v in views]), torch.cat([v[1] for v in views])
+        results += _full_resolution_many(net, rb, wm, small, msmall, foreground=True)
+    return results
+
+
+def _packed_batches(images_u8, masks_u8, device, view, batch_size):
+    """The arguments of enhance_many, checked, and per batch of at most batch_size images the two uploaded arenas."""
+    if view not in ("float", "pil"):
+        raise ValueError(f"view must be 'float' or 'pil', got {view!r}")
+    if len(images_u8) != len(masks_u8):
+        raise ValueError(f"one mask per image: {len(images_u8)} images, {len(masks_u8)} masks")
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    device = torch.device(device)
+
+    def batches():
+        for b0 in range(0, len(images_u8), batch_size):
+            # view="pil": the images go up with the channel count the files have (every ragged entry takes RGBA as it is);
+            # view="float": alpha dropped on the host, as enhance does (the float view needs RGB)
+            imgs = [np.ascontiguousarray(np.asarray(x)[..., :4 if view == "pil" else 3]) for x in images_u8[b0:b0 + batch_size]]
+            rb = ops.RaggedBytes.pack(imgs, device)
+            yield rb, ops.RaggedBytes.pack([np.array(m, dtype=np.uint8) for m in masks_u8[b0:b0 + batch_size]], device)
+    return batches()
+
+
+def _full_resolution_many(net, rb, wm, small, msmall, foreground):
+    """The encoder once on the [n,3,320,320] views, the full-resolution pass of the batch in one ragged call (foreground: the
+    foreground-aware one) and one download -> the batch's HxWx3 uint8 arrays."""
+    if isinstance(net, model_mod.TriSpaceRegNet):
+        coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)
+        out = (ops.trispace_foreground_u8hwc_ragged if foreground else ops.trispace_forward_u8hwc_ragged)(rb, coeffs, wm)
+    else:
+        knots = net.predict_knots(small * msmall)
+        L, R, H = knots[:, :net.curve_break_1], knots[:, net.curve_break_1:net.curve_break_2], knots[:, net.curve_break_2:]
+        cl = net.curllayer
+        layer = ops.curl_layer_foreground_u8hwc_ragged if foreground else ops.curl_layer_forward_u8hwc_ragged
+        out, _ = layer(rb, L[:, :cl.num_lab_points].contiguous(), R[:, :cl.num_rgb_points].contiguous(),
+                       H[:, :cl.num_hsv_points].contiguous(), wm)
+    host = out.arena.cpu().numpy()  # one download per batch
+    return [host[o:o + h * w * 3].reshape(h, w, 3).copy() for (h, w), o in zip(out.shapes, out.offsets)]
 
 
 def infer(argv=None):

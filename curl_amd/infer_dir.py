@@ -4,7 +4,8 @@ whole batch of differently sized images in one ragged call (infer.enhance_many).
     python -m curl_amd.infer_dir --img_dir in/ --mask_dir masks/ --model_file ckpt.pt --out_dir out/
 
 A mask belongs to the image with the same file stem (in/a.png <- masks/a.png, or any other extension).  Every output is
-written as <out_dir>/<stem>.png.  The flags shared with curl_amd.infer mean what they mean there.
+written as <out_dir>/<stem>.png.  The flags shared with curl_amd.infer mean what they mean there; --foreground_masks takes
+the foreground-aware ragged call (infer.enhance_many_foreground): the same files, the masked-out regions never computed.
 """
 import argparse
 import os
@@ -12,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .infer import build_net, enhance_many
+from .infer import build_net, enhance_many, enhance_many_foreground
 
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
@@ -36,7 +37,11 @@ def main(argv=None):
     parser.add_argument("--polynomial_order", type=int, default=4, choices=(1, 2, 3, 4))
     parser.add_argument("--encoder_view", choices=("float", "pil"), default="float")
     parser.add_argument("--batch_size", type=int, default=32, help="images per ragged call")
+    parser.add_argument("--foreground_masks", action="store_true",
+                        help="the masks are segmentation masks: regions they white out entirely are never read or computed "
+                             "(the same output bytes)")
     args = parser.parse_args(argv)
+    enhance = enhance_many_foreground if args.foreground_masks else enhance_many
     from PIL import Image
     images, masks = _by_stem(args.img_dir), _by_stem(args.mask_dir)
     for stem, path in images.items():
@@ -55,7 +60,7 @@ def main(argv=None):
                 img = np.repeat(img[..., None], 3, axis=2)
             imgs.append(img)
             ms.append(np.asarray(Image.open(masks[stem]).convert("L")))
-        for stem, out in zip(batch, enhance_many(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)):
+        for stem, out in zip(batch, enhance(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)):
             Image.fromarray(out).save(os.path.join(args.out_dir, stem + ".png"))
     return 0
 

@@ -1236,6 +1236,72 @@ def curl_layer_forward_u8hwc_ragged(images, L, R, H, white_masks=None):
     return out, reg
 
 
+def _ragged_fg_masks(images, fg_masks):
+    """The foreground entries' masks, held to the images before anything is packed or uploaded: required, one uint8 [H,W]
+    mask of each image's size (_ragged_inputs holds the packed arenas to the same)."""
+    if fg_masks is None:
+        raise ValueError("fg_masks is required (one uint8 [H,W] 'L' mask per image)")
+
+    def sizes(x):
+        return [tuple(s) for s in x.shapes] if isinstance(x, RaggedBytes) else [tuple(t.shape) for t in x]
+    want, got = [s[:2] for s in sizes(images)], sizes(fg_masks)
+    if len(got) != len(want):
+        raise ValueError(f"fg_masks must hold one mask per image ({len(want)}), got {len(got)}")
+    if got != want:
+        raise ValueError(f"fg_masks must be uint8 [H,W] masks of the images' sizes {want}, got {got}")
+    if not isinstance(fg_masks, RaggedBytes) and any(not str(t.dtype).endswith("uint8") for t in fg_masks):
+        raise ValueError(f"fg_masks must be uint8 [H,W] masks, got {[str(t.dtype) for t in fg_masks]}")
+
+
+def trispace_foreground_u8hwc_ragged(images, coeffs, fg_masks):
+    """trispace_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result:
+    wavefronts whose mask bytes are all 0 store white and never read their pixels, workgroups of such wavefronts stage no
+    table (curl_trispace_fwd_ragged_fg_u8hwc).  The same inputs, fg_masks required; the cached plan of a shape list is the
+    plain call's.  -> RaggedBytes of the [H,W,3] outputs."""
+    empty, device = _ragged_empty(images, coeffs.device if isinstance(coeffs, torch.Tensor) else None)
+    _ragged_fg_masks(images, fg_masks)
+    if empty:
+        return RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], [])
+    lib = _lib.load()
+    rb, wm = _ragged_inputs(images, fg_masks, device)
+    _check_coeffs(coeffs, len(rb))
+    _check_same_device([("images", rb.arena), ("coeffs", coeffs)])
+    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
+    nc = _nc_arg(c.shape[3])
+    plan, out = _ragged_arenas(rb, wm, nc)
+    with torch.cuda.device(rb.device):
+        rc = lib.curl_trispace_fwd_ragged_fg_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), c.data_ptr(), wm.arena.data_ptr(), wm.arena.numel(),
+                                                   out.arena.data_ptr(), out.arena.numel(), plan.host.data_ptr(), plan.dev.data_ptr(),
+                                                   plan.nbytes, nc, 0, _stream(rb.arena))
+    _lib.check(rc, "curl_trispace_fwd_ragged_fg_u8hwc")
+    return out
+
+
+def curl_layer_foreground_u8hwc_ragged(images, L, R, H, fg_masks):
+    """curl_layer_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result and
+    the same reg (curl_layer_fwd_ragged_fg_u8hwc).  -> (RaggedBytes of the [H,W,3] outputs, reg [B])."""
+    empty, device = _ragged_empty(images, L.device if isinstance(L, torch.Tensor) else None)
+    _ragged_fg_masks(images, fg_masks)
+    if empty:
+        return (RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], []),
+                torch.zeros(0, dtype=torch.float32, device=device))
+    lib = _lib.load()
+    rb, wm = _ragged_inputs(images, fg_masks, device)
+    B = len(rb)
+    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
+    _check_same_device([("images", rb.arena), ("L", Lc), ("R", Rc), ("H", Hc)])
+    plan, out = _ragged_arenas(rb, wm, 0)
+    reg = torch.empty(B, dtype=torch.float32, device=rb.device)
+    ws, nbytes = _workspace(B, n_knots, rb.device)
+    with torch.cuda.device(rb.device):
+        rc = lib.curl_layer_fwd_ragged_fg_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
+                                                wm.arena.data_ptr(), wm.arena.numel(), out.arena.data_ptr(), out.arena.numel(),
+                                                reg.data_ptr(), ws.data_ptr(), nbytes, plan.host.data_ptr(), plan.dev.data_ptr(),
+                                                plan.nbytes, Kl, Kr, Kh, 0, _stream(rb.arena))
+    _lib.check(rc, "curl_layer_fwd_ragged_fg_u8hwc")
+    return out, reg
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
