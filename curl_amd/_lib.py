@@ -158,6 +158,13 @@ SIGNATURES_RAGGED_FG = {
     "curl_layer_fwd_ragged_fg_u8hwc": (_i, list(SIGNATURES_RAGGED["curl_layer_fwd_ragged_u8hwc"][1])),
 }
 
+# include/curl_hip_ragged_score.h: the exact score of a ragged byte batch (an eighth table, for the same reason; the workspace
+# query takes HOST memory and makes no HIP call)
+SIGNATURES_RAGGED_SCORE = {
+    "curl_ragged_score_workspace_bytes": (_sz, [_c_f]),
+    "curl_sse_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _u, _c_f]),
+}
+
 _lib = None
 
 
@@ -182,7 +189,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()) + \
-            list(SIGNATURES_RAGGED_FG.items()):
+            list(SIGNATURES_RAGGED_FG.items()) + list(SIGNATURES_RAGGED_SCORE.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -747,7 +747,8 @@ extern "C" {
 //         curl_poly_layer_f32 the degree in the high half of num_variables (include/curl_hip_poly.h)
 // 0.1.16: the ragged byte entries: a batch of images of different sizes in one launch per class (include/curl_hip_ragged.h)
 // 0.1.18: the ragged byte entries, foreground-aware: dead wavefronts store white unread (include/curl_hip_ragged_fg.h)
-int curl_version(void) { return 118; }
+// 0.1.19: the exact score of a ragged byte batch: per-image integer SSE and pixel count (include/curl_hip_ragged_score.h)
+int curl_version(void) { return 119; }
 
 const char* curl_last_error(void) { return g_err; }
 

@@ -149,9 +149,58 @@ def _packed_batches(images_u8, masks_u8, device, view, batch_size):
     return batches()
 
 
+@torch.no_grad()
+def enhance_and_score_many(net, images_u8, masks_u8, targets_u8, device, view="pil", batch_size=32, foreground=False):
+    """enhance_many (foreground=True: enhance_many_foreground) and the score of every output against its target:
+    targets_u8[i] HxWx3|4 uint8 of image i's size (alpha is dropped on the host) -> (outputs, psnr).  The outputs are those
+    functions' arrays, byte for byte; psnr is a float64 numpy array [N], the masked PSNR of evaluate.py:102 with the white mask
+    as the metric's mask, exact on the bytes (ops.psnr_u8hwc_ragged): nan where the mask keeps no pixel, inf for an output
+    equal to its target.  Per batch the out arena stays on the device, the targets go up as one RGB arena, the mask arena is
+    the one already uploaded, and the score is ONE call; no float image is made."""
+    if len(targets_u8) != len(images_u8):
+        raise ValueError(f"one target per image: {len(images_u8)} images, {len(targets_u8)} targets")
+    targets = []
+    for i, (img, tgt) in enumerate(zip(images_u8, targets_u8)):
+        t = np.asarray(tgt)
+        if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] not in (3, 4):
+            raise ValueError(f"target {i} must be uint8 HxWx3|4, got {t.dtype} {t.shape}")
+        if t.shape[:2] != np.asarray(img).shape[:2]:
+            raise ValueError(f"target {i} is {t.shape[0]}x{t.shape[1]}, its image {np.asarray(img).shape[0]}x{np.asarray(img).shape[1]}")
+        targets.append(t)
+    results, scores = [], []
+    for k, (rb, wm) in enumerate(_packed_batches(images_u8, masks_u8, device, view, batch_size)):
+        small, msmall = _encoder_views(rb, wm, view)
+        out = _full_resolution_device(net, rb, wm, small, msmall, foreground)
+        tg = ops.RaggedBytes.pack([np.ascontiguousarray(t[..., :3]) for t in targets[k * batch_size:(k + 1) * batch_size]], rb.device)
+        psnr = ops.psnr_u8hwc_ragged(out, tg, wm)  # one score call per batch, on the arenas the batch already has
+        results += _download(out)
+        scores.append(psnr.cpu().numpy())
+    return results, np.concatenate(scores) if scores else np.zeros(0, dtype=np.float64)
+
+
+def _encoder_views(rb, wm, view):
+    """The [n,3,320,320] views of a packed batch as enhance_many and enhance_many_foreground make them (their bodies spell the
+    calls out; tests read them there)."""
+    if view == "pil":
+        return ops.encoder_view_u8hwc_ragged(rb, wm)
+    views = [encoder_view(ops.u8hwc_to_f32chw(rb.image(i)[None]), wm.image(i)[None, None].float() / 255.0) for i in range(len(rb))]
+    return torch.cat([v[0] for v in views]), torch.cat([v[1] for v in views])
+
+
 def _full_resolution_many(net, rb, wm, small, msmall, foreground):
     """The encoder once on the [n,3,320,320] views, the full-resolution pass of the batch in one ragged call (foreground: the
     foreground-aware one) and one download -> the batch's HxWx3 uint8 arrays."""
+    return _download(_full_resolution_device(net, rb, wm, small, msmall, foreground))
+
+
+def _download(out):
+    """One download of an out arena -> the batch's HxWx3 uint8 arrays."""
+    host = out.arena.cpu().numpy()
+    return [host[o:o + h * w * 3].reshape(h, w, 3).copy() for (h, w), o in zip(out.shapes, out.offsets)]
+
+
+def _full_resolution_device(net, rb, wm, small, msmall, foreground):
+    """The device part of _full_resolution_many -> the RaggedBytes of the outputs, still on the device."""
     if isinstance(net, model_mod.TriSpaceRegNet):
         coeffs = torch.stack(net.generate_coefficients(small, msmall), 1)
         out = (ops.trispace_foreground_u8hwc_ragged if foreground else ops.trispace_forward_u8hwc_ragged)(rb, coeffs, wm)
@@ -162,8 +211,7 @@ def _full_resolution_many(net, rb, wm, small, msmall, foreground):
         layer = ops.curl_layer_foreground_u8hwc_ragged if foreground else ops.curl_layer_forward_u8hwc_ragged
         out, _ = layer(rb, L[:, :cl.num_lab_points].contiguous(), R[:, :cl.num_rgb_points].contiguous(),
                        H[:, :cl.num_hsv_points].contiguous(), wm)
-    host = out.arena.cpu().numpy()  # one download per batch
-    return [host[o:o + h * w * 3].reshape(h, w, 3).copy() for (h, w), o in zip(out.shapes, out.offsets)]
+    return out
 
 
 def infer(argv=None):

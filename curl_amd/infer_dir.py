@@ -6,14 +6,20 @@ whole batch of differently sized images in one ragged call (infer.enhance_many).
 A mask belongs to the image with the same file stem (in/a.png <- masks/a.png, or any other extension).  Every output is
 written as <out_dir>/<stem>.png.  The flags shared with curl_amd.infer mean what they mean there; --foreground_masks takes
 the foreground-aware ragged call (infer.enhance_many_foreground): the same files, the masked-out regions never computed.
+
+--gt_dir G scores every output against the target of the same stem in G (infer.enhance_and_score_many: the masked PSNR of
+the reference's Evaluator, exact on the bytes, one score call per batch): one `stem<TAB>psnr` line per image, then
+`mean<TAB>value<TAB>left_out` -- the mean over the images whose PSNR is finite and the number of images left out of it.
+--scores_file F writes the same lines to F.
 """
 import argparse
+import math
 import os
 
 import numpy as np
 import torch
 
-from .infer import build_net, enhance_many, enhance_many_foreground
+from .infer import build_net, enhance_and_score_many, enhance_many, enhance_many_foreground
 
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
@@ -25,6 +31,12 @@ def _by_stem(folder):
         if ext.lower() in IMAGE_EXTENSIONS and stem not in out:
             out[stem] = os.path.join(folder, name)
     return out
+
+
+def _rgb(path):
+    from PIL import Image
+    img = np.asarray(Image.open(path))
+    return np.repeat(img[..., None], 3, axis=2) if img.ndim == 2 else img
 
 
 def main(argv=None):
@@ -40,28 +52,49 @@ def main(argv=None):
     parser.add_argument("--foreground_masks", action="store_true",
                         help="the masks are segmentation masks: regions they white out entirely are never read or computed "
                              "(the same output bytes)")
+    parser.add_argument("--gt_dir", type=str, default=None,
+                        help="Folder of target images, matched to the images by file stem: print every output's masked PSNR "
+                             "against its target and the mean over the finite ones")
+    parser.add_argument("--scores_file", type=str, default=None, help="with --gt_dir: also write the score lines to this file")
     args = parser.parse_args(argv)
+    if args.scores_file is not None and args.gt_dir is None:
+        parser.error("--scores_file needs --gt_dir")
     enhance = enhance_many_foreground if args.foreground_masks else enhance_many
     from PIL import Image
     images, masks = _by_stem(args.img_dir), _by_stem(args.mask_dir)
+    targets = _by_stem(args.gt_dir) if args.gt_dir is not None else None
     for stem, path in images.items():
         if stem not in masks:
             raise FileNotFoundError(f"no mask for {path}: nothing named {stem}.* in {args.mask_dir}")
+        if targets is not None and stem not in targets:
+            raise FileNotFoundError(f"no target for {path}: nothing named {stem}.* in {args.gt_dir}")
     device = torch.device("cuda:0")
     net = build_net(args.model_file, device, args.arch, args.polynomial_order)
     os.makedirs(args.out_dir, exist_ok=True)
     stems = list(images)
+    lines, finite = [], []
     for b0 in range(0, len(stems), args.batch_size):  # a batch of files in memory at a time
         batch = stems[b0:b0 + args.batch_size]
-        imgs, ms = [], []
-        for stem in batch:
-            img = np.asarray(Image.open(images[stem]))
-            if img.ndim == 2:
-                img = np.repeat(img[..., None], 3, axis=2)
-            imgs.append(img)
-            ms.append(np.asarray(Image.open(masks[stem]).convert("L")))
-        for stem, out in zip(batch, enhance(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)):
+        imgs = [_rgb(images[stem]) for stem in batch]
+        ms = [np.asarray(Image.open(masks[stem]).convert("L")) for stem in batch]
+        if targets is None:
+            outs = enhance(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)
+        else:
+            outs, psnr = enhance_and_score_many(net, imgs, ms, [_rgb(targets[stem]) for stem in batch], device, view=args.encoder_view,
+                                                batch_size=args.batch_size, foreground=args.foreground_masks)
+            for stem, value in zip(batch, psnr):
+                lines.append(f"{stem}\t{float(value)!r}")
+                if math.isfinite(value):
+                    finite.append(float(value))
+        for stem, out in zip(batch, outs):
             Image.fromarray(out).save(os.path.join(args.out_dir, stem + ".png"))
+    if targets is not None:
+        mean = sum(finite) / len(finite) if finite else float("nan")
+        lines.append(f"mean\t{mean!r}\t{len(lines) - len(finite)}")
+        print("\n".join(lines))
+        if args.scores_file is not None:
+            with open(args.scores_file, "w") as f:
+                f.write("\n".join(lines) + "\n")
     return 0
 
 

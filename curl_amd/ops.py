@@ -1302,6 +1302,81 @@ def curl_layer_foreground_u8hwc_ragged(images, L, R, H, fg_masks):
     return out, reg
 
 
+# ------------------------------------------------------------------ the score of a ragged batch (include/curl_hip_ragged_score.h)
+def _score_shapes(x, name):
+    """The [(H, W)] of one side of a score call, held to uint8 [H,W,3] before anything is packed or uploaded."""
+    if isinstance(x, RaggedBytes):
+        if any(c != 3 for c in x.channels):
+            raise ValueError(f"{name} must hold uint8 [H,W,3] images, got channels {x.channels}")
+        return [tuple(s) for s in x.shapes]
+    shapes = []
+    for k, t in enumerate(x):
+        shape = tuple(getattr(t, "shape", ()))
+        if not str(getattr(t, "dtype", "")).endswith("uint8") or len(shape) != 3 or shape[2] != 3 or 0 in shape:
+            raise ValueError(f"image {k} of {name} must be uint8 [H,W,3], got {getattr(t, 'dtype', type(t).__name__)} {shape}")
+        shapes.append((int(shape[0]), int(shape[1])))
+    return shapes
+
+
+def _score_masks(masks, shapes):
+    """The optional masks of a score call, held to the images: one uint8 [H,W] mask of each image's size."""
+    if masks is None:
+        return
+    if isinstance(masks, RaggedBytes):
+        got = [tuple(s) for s in masks.shapes] if all(c == 1 for c in masks.channels) else None
+    else:
+        masks = list(masks)
+        if any(not str(getattr(t, "dtype", "")).endswith("uint8") for t in masks):
+            raise ValueError(f"masks must be uint8 [H,W] masks, got {[str(getattr(t, 'dtype', type(t).__name__)) for t in masks]}")
+        got = [tuple(t.shape) for t in masks]
+    if got != shapes:
+        raise ValueError(f"masks must be one uint8 [H,W] mask per image, of the images' sizes {shapes}, got {got}")
+
+
+def sse_u8hwc_ragged(a, b, masks=None):
+    """The exact masked squared error of two batches of byte images of different sizes, every image in one pass
+    (curl_sse_ragged_u8hwc): a and b a RaggedBytes or a list of uint8 [H,W,3] images of the same shape list, masks None or one
+    uint8 [H,W] mask per image (a RaggedBytes or a list).  -> int64 [B,2] on the device: [i,0] the sum over the pixels whose
+    mask byte is not 0 (all pixels without masks) and the 3 channels of (a - b)^2, [i,1] the number of those pixels.  Integer
+    arithmetic throughout: the same bits on every call, for an image alone or in any company and order."""
+    shapes = _score_shapes(a, "a")
+    if _score_shapes(b, "b") != shapes:
+        raise ValueError(f"a and b must hold images of the same sizes, got {shapes} and {_score_shapes(b, 'b')}")
+    _score_masks(masks, shapes)
+    if not shapes:
+        device = next((x.device for x in (a, b) if isinstance(x, RaggedBytes)), None)
+        return torch.zeros((0, 2), dtype=torch.int64, device=device)
+    lib = _lib.load()
+    ra, wm = _ragged_inputs(a, masks, None)
+    rb = b if isinstance(b, RaggedBytes) else RaggedBytes.pack(list(b), ra.device)
+    _need_device(rb.arena, "b")
+    _check_same_device([("a", ra.arena), ("b", rb.arena)])
+    B = len(ra)
+    plan = _ragged_plan(ra.shapes, [3] * B, wm is not None, 0, ra.device)
+    if ra.offsets != plan.out_off or rb.offsets != plan.out_off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    sums = torch.empty((B, 2), dtype=torch.int64, device=ra.device)
+    nbytes = lib.curl_ragged_score_workspace_bytes(plan.host.data_ptr())
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=ra.device)
+    with torch.cuda.device(ra.device):
+        rc = lib.curl_sse_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
+                                       _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
+                                       sums.data_ptr(), sums.numel() * 8, ws.data_ptr(), nbytes, plan.host.data_ptr(),
+                                       plan.dev.data_ptr(), plan.nbytes, 0, _stream(ra.arena))
+    _lib.check(rc, "curl_sse_ragged_u8hwc")
+    return sums
+
+
+def psnr_u8hwc_ragged(a, b, masks=None):
+    """The masked PSNR of every image of a ragged byte batch against its target, float64 [B] on the device:
+    10 * log10(255^2 * 3 N / SSE) from sse_u8hwc_ragged's integers (no synchronisation) -- metric.py:35-64 on the bytes / 255,
+    without its float32 sum.  nan for an image whose mask keeps no pixel (0 / 0), inf for equal images (1 / 0), as there."""
+    sums = sse_u8hwc_ragged(a, b, masks).to(torch.float64)  # exact: both columns are below 2^53
+    return 10.0 * torch.log10(255.0 ** 2 * 3.0 * sums[:, 1] / sums[:, 0])
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
