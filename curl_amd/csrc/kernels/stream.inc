@@ -332,7 +332,8 @@ __global__ __launch_bounds__(256, Op::kMinWavesPerSimd) void stream_kernel(Strea
     chunk = (blockIdx.x & 7u) * a.xcd_per + (blockIdx.x >> 3);
     if (chunk >= a.blocks_per_image) return;  // the padding of the last eighth (wave-uniform)
   }
-  __builtin_assume(a.n <= (1u << 28));  // H*W <= 2^30 (checked on the host): byte offsets fit 32 bits
+  // H*W <= 2^30 (checked on the host): n <= 2^28 float4 groups, or 2^30 pixels on the scalar path -- byte offsets fit 32 bits
+  __builtin_assume(a.n <= (1u << 30) / VEC);
   const float* table = a.coef ? a.coef + (size_t)img * a.coef_stride : nullptr;
   __shared__ __attribute__((aligned(16))) float s_table[Op::kLdsFloats > 0 ? Op::kLdsFloats : 1];
   unsigned row = 0, base = chunk * (blockDim.x * U) + threadIdx.x;

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256, Op::kMinWavesPerSimd) void stream_fg_kernel(St
   static_assert(Op::kUnroll == 1 || Op::kSingleTileShape, "one group per lane");
   static_assert(!NT || VEC == 4, "the byte path takes plain accesses");
   const unsigned img = blockIdx.y, chunk = blockIdx.x;
-  __builtin_assume(a.n <= (1u << 28));
+  __builtin_assume(a.n <= (1u << 30) / VEC);  // (groups of VEC pixels: the byte class counts pixels, up to 2^30)
   const float* table = a.coef ? a.coef + (size_t)img * a.coef_stride : nullptr;
   unsigned row = 0, base = chunk * blockDim.x + threadIdx.x;
   bool valid = true;
