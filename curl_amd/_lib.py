@@ -165,6 +165,18 @@ SIGNATURES_RAGGED_SCORE = {
     "curl_sse_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _u, _c_f]),
 }
 
+# include/curl_hip_ragged_msssim.h: the MS-SSIM statistics of a ragged byte batch (a ninth table, for the same reason; the plan
+# functions and the workspace query take and fill HOST memory and make no HIP call)
+SIGNATURES_RAGGED_MSSSIM = {
+    "curl_msssim_ragged_plan_bytes": (_sz, [_i]),
+    "curl_msssim_ragged_plan": (_i, [_i, _c_f, _c_f, _i, _c_f, _sz]),
+    "curl_msssim_ragged_workspace_bytes": (_sz, [_c_f]),
+    "curl_msssim_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _i, _u, _c_f]),
+}
+# the plan's layout (int32 words): CURL_MSSSIM_RAGGED_STAMP, _HEADER_WORDS, _DESC_WORDS, _LEVEL_WORD, _LEVEL_WORDS
+MSSSIM_RAGGED_STAMP, MSSSIM_RAGGED_HEADER_WORDS, MSSSIM_RAGGED_DESC_WORDS, MSSSIM_RAGGED_LEVEL_WORD, MSSSIM_RAGGED_LEVEL_WORDS = \
+    0x4D535231, 32, 64, 16, 8
+
 _lib = None
 
 
@@ -189,7 +201,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()) + \
-            list(SIGNATURES_RAGGED_FG.items()) + list(SIGNATURES_RAGGED_SCORE.items()):
+            list(SIGNATURES_RAGGED_FG.items()) + list(SIGNATURES_RAGGED_SCORE.items()) + list(SIGNATURES_RAGGED_MSSSIM.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

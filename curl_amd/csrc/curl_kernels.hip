@@ -26,6 +26,7 @@
 #include "../../include/curl_hip_view_ragged.h"
 #include "../../include/curl_hip_ragged_fg.h"
 #include "../../include/curl_hip_ragged_score.h"
+#include "../../include/curl_hip_ragged_msssim.h"
 #include "curl_math_bwd.h"
 #include "curl_math_poly.h"
 #include "curl_math_loss.h"
@@ -227,6 +228,7 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/stream_ragged.inc"
 #include "kernels/stream_ragged_fg.inc"
 #include "kernels/score_ragged.inc"
+#include "kernels/msssim_ragged.inc"
 #include "kernels/encoder_view_ragged.inc"
 #include "kernels/host_api.inc"
 #include "kernels/host_api_grad.inc"
@@ -234,4 +236,5 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/host_api_ragged.inc"
 #include "kernels/host_api_ragged_fg.inc"
 #include "kernels/host_api_ragged_score.inc"
+#include "kernels/host_api_ragged_msssim.inc"
 #include "kernels/host_api_view.inc"

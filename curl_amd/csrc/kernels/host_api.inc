@@ -748,7 +748,8 @@ extern "C" {
 // 0.1.16: the ragged byte entries: a batch of images of different sizes in one launch per class (include/curl_hip_ragged.h)
 // 0.1.18: the ragged byte entries, foreground-aware: dead wavefronts store white unread (include/curl_hip_ragged_fg.h)
 // 0.1.19: the exact score of a ragged byte batch: per-image integer SSE and pixel count (include/curl_hip_ragged_score.h)
-int curl_version(void) { return 119; }
+// 0.1.20: the MS-SSIM statistics of a ragged byte batch: six launches from the bytes (include/curl_hip_ragged_msssim.h)
+int curl_version(void) { return 120; }
 
 const char* curl_last_error(void) { return g_err; }
 

@@ -1,0 +1,159 @@
+// host_api_ragged_msssim.inc -- part of curl_kernels.hip (one translation unit; included after host_api_ragged.inc, whose
+// arena rule, hash and error text it uses, and host_api.inc, whose ssim_window it uses).  The entry points of
+// include/curl_hip_ragged_msssim.h.
+// ------------------------------------------------------------------------------------------------
+// host side: the MS-SSIM statistics of a batch of byte images of different sizes
+// ------------------------------------------------------------------------------------------------
+static size_t ms_plan_words(int B) { return kMsHeaderWords + (size_t)B * kMsDescWords; }
+
+static int ms_build(int B, const int* H, const int* W, bool has_mask, int* p) {
+  uint64_t hash = 1469598103934665603ull;
+  hash = ragged_hash_word(ragged_hash_word(ragged_hash_word(hash, kMsStamp), has_mask), (uint32_t)B);
+  for (int i = 0; i < B; ++i) {
+    if (H[i] <= 0 || W[i] <= 0) return fail(CURL_E_SHAPE, "ragged batch: every H and W must be positive");
+    if ((uint64_t)H[i] * (uint64_t)W[i] > (1ull << 30)) return fail(CURL_E_SHAPE, "ragged batch: an image's H*W exceeds 2^30 pixels");
+    if ((H[i] >> MSSSIM_LEVELS) < 1 || (W[i] >> MSSSIM_LEVELS) < 1) {  // metric.py:185-192 pools once more after the fifth level
+      snprintf(g_err, sizeof(g_err), "ragged MS-SSIM: image %d is %dx%d; MS-SSIM needs H, W >= 32 (five pyramid levels, each followed by a 2x2 pooling)",
+               i, H[i], W[i]);
+      return CURL_E_SHAPE;
+    }
+    hash = ragged_hash_word(ragged_hash_word(hash, (uint32_t)H[i]), (uint32_t)W[i]);
+  }
+  memset(p, 0, ms_plan_words(B) * sizeof(int));
+  const auto align = [](uint64_t v) { return (v + kRaggedAlign - 1) & ~(kRaggedAlign - 1); };
+  uint64_t grid[kMsLevels] = {0, 0, 0, 0, 0}, planes = 0;
+  RaggedArenas arenas;
+  for (int i = 0; i < B; ++i) {
+    int* d = p + kMsHeaderWords + (size_t)i * kMsDescWords;
+    d[MD_INDEX] = i, d[MD_H] = H[i], d[MD_W] = W[i];
+    uint64_t off_img, off_mask, off_rgb;
+    if (int rc = arenas.place((uint64_t)H[i] * (uint64_t)W[i], 3, has_mask, off_img, off_mask, off_rgb)) return rc;
+    put64(d + MD_RGB_OFF, off_rgb), put64(d + MD_MASK_OFF, off_mask);
+    for (int l = 0; l < kMsLevels; ++l) {
+      int* v = d + kMsLevelWord + l * kMsLevelWords;
+      const int h = H[i] >> l, w = W[i] >> l;
+      const uint64_t tiles = (uint64_t)ssim_tiles(h, w);
+      if (grid[l] + tiles > 0x7fffffffull) return fail(CURL_E_SHAPE, "ragged batch: a launch's grid exceeds 2^31 - 1 workgroups");
+      v[ML_H] = h, v[ML_W] = w, v[ML_TILES_X] = (int)ssim_tiles_x(w), v[ML_TILES] = (int)tiles, v[ML_FIRST] = (int)grid[l];
+      grid[l] += tiles;
+      if (l >= 1) {
+        planes = align(planes);
+        put64(v + ML_PLANES, planes);
+        planes += 6ull * sizeof(float) * (uint64_t)h * (uint64_t)w;
+      }
+    }
+  }
+  uint64_t pair0[kMsLevels], pairs = 0;
+  for (int l = 0; l < kMsLevels; ++l) pair0[l] = pairs, pairs += grid[l];
+  if (pairs > 0x7fffffffull) return fail(CURL_E_SHAPE, "ragged batch: a launch's grid exceeds 2^31 - 1 workgroups");
+  for (int i = 0; i < B; ++i)
+    for (int l = 0; l < kMsLevels; ++l) {
+      int* v = p + kMsHeaderWords + (size_t)i * kMsDescWords + kMsLevelWord + l * kMsLevelWords;
+      v[ML_PAIR] = (int)(pair0[l] + (uint64_t)v[ML_FIRST]);
+    }
+  planes = align(planes);
+  p[MH_STAMP] = (int)kMsStamp, p[MH_B] = B, p[MH_OP] = (int)kMsOp, p[MH_HAS_MASK] = has_mask, p[MH_LAUNCHES] = kMsLevels + 1;
+  for (int l = 0; l < kMsLevels; ++l) p[MH_GRID0 + l] = (int)grid[l], p[MH_PAIR0 + l] = (int)pair0[l];
+  put64(p + MH_RGB_BYTES, arenas.out), put64(p + MH_MASK_BYTES, arenas.mask), put64(p + MH_HASH, hash);
+  put64(p + MH_PARTIAL_OFF, planes), put64(p + MH_WS_BYTES, planes + pairs * 2 * sizeof(double));
+  return 0;
+}
+
+// A host plan is the caller's memory: what the entries read from it is checked for being a plan's
+static int ms_host_plan(const void* host_plan) {
+  if (!host_plan) return fail(CURL_E_NULL, "host_plan is NULL");
+  if ((uintptr_t)host_plan % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the host plan must be 8-byte aligned");
+  const int* p = static_cast<const int*>(host_plan);
+  bool ok = (unsigned)p[MH_STAMP] == kMsStamp && p[MH_B] >= 1 && p[MH_B] <= kRaggedMaxImages;
+  uint64_t pairs = 0;
+  for (int l = 0; ok && l < kMsLevels; ++l) {
+    ok = p[MH_GRID0 + l] >= p[MH_B] && (uint64_t)(unsigned)p[MH_PAIR0 + l] == pairs;
+    pairs += (uint64_t)(unsigned)p[MH_GRID0 + l];
+  }
+  ok = ok && get64(p + MH_PARTIAL_OFF) % 8 == 0 && get64(p + MH_WS_BYTES) == get64(p + MH_PARTIAL_OFF) + pairs * 2 * sizeof(double);
+  if (!ok) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: host_plan holds no plan (curl_msssim_ragged_plan)");
+  return 0;
+}
+
+extern "C" {
+
+size_t curl_msssim_ragged_plan_bytes(int B) {
+  if (B < 1 || B > kRaggedMaxImages) return 0;
+  return ms_plan_words(B) * sizeof(int);
+}
+
+int curl_msssim_ragged_plan(int B, const int* H, const int* W, int has_mask, void* host_buf, size_t bytes) {
+  g_err[0] = 0;
+  if (!H || !W) return fail(CURL_E_NULL, "H / W is NULL");
+  if (!host_buf) return fail(CURL_E_NULL, "host_buf is NULL");
+  if (B < 1) return fail(CURL_E_SHAPE, "ragged batch: B must be positive");
+  if (B > kRaggedMaxImages) return fail(CURL_E_SHAPE, "B exceeds 65535 images per call");
+  if ((uintptr_t)host_buf % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer must be 8-byte aligned");
+  if (bytes < ms_plan_words(B) * sizeof(int))
+    return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer is too small (curl_msssim_ragged_plan_bytes)");
+  return ms_build(B, H, W, has_mask != 0, static_cast<int*>(host_buf));
+}
+
+size_t curl_msssim_ragged_workspace_bytes(const void* host_plan) {
+  const int rc = ms_host_plan(host_plan);
+  g_err[0] = 0;
+  if (rc || static_cast<const int*>(host_plan)[MH_OP] != (int)kMsOp) return 0;
+  return (size_t)get64(static_cast<const int*>(host_plan) + MH_WS_BYTES);
+}
+
+int curl_msssim_ragged_u8hwc(const uint8_t* a_arena, size_t a_bytes, const uint8_t* b_arena, size_t b_bytes,
+                             const uint8_t* mask_arena, size_t mask_bytes, double* stats, size_t stats_bytes, void* workspace,
+                             size_t workspace_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes, int window_size,
+                             unsigned flags, curl_stream_t stream) {
+  g_err[0] = 0;
+  // check_ragged's checks in its order and wording, on this header's plan; then this entry's own
+  if (!a_arena || !b_arena) return fail(CURL_E_NULL, "arena pointer is NULL");
+  if (!plan_dev) return fail(CURL_E_NULL, "plan_dev is NULL");
+  if (int rc = ms_host_plan(host_plan)) return rc;
+  if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (flags must be 0)");
+  const int* p = static_cast<const int*>(host_plan);
+  if (p[MH_OP] != (int)kMsOp) return fail(CURL_E_WORKSPACE, "ragged batch: the plan was made for another operator");
+  if (mask_arena && !p[MH_HAS_MASK]) return fail(CURL_E_WORKSPACE, "ragged batch: a mask arena with a plan that was made without masks");
+  if ((uintptr_t)plan_dev % 8) return fail(CURL_E_WORKSPACE, "ragged batch: plan_dev must be 8-byte aligned");
+  const unsigned B = (unsigned)p[MH_B];
+  if (plan_bytes < ms_plan_words((int)B) * sizeof(int))
+    return fail(CURL_E_WORKSPACE, "ragged batch: plan_dev is too small (curl_msssim_ragged_plan_bytes)");
+  const uint64_t rgb_bytes = get64(p + MH_RGB_BYTES), ws_bytes = get64(p + MH_WS_BYTES), partial_off = get64(p + MH_PARTIAL_OFF);
+  if (a_bytes < rgb_bytes) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: the a arena is smaller than the plan's");
+  if (b_bytes < rgb_bytes) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: the b arena is smaller than the plan's");
+  if (mask_arena && mask_bytes < get64(p + MH_MASK_BYTES)) return fail(CURL_E_WORKSPACE, "ragged batch: the mask arena is smaller than the plan's");
+  if (!stats) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: stats is NULL");
+  if ((uintptr_t)stats % 8) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: stats must be 8-byte aligned");
+  if (stats_bytes < (size_t)B * 2 * kMsLevels * sizeof(double)) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: stats is too small (80 bytes per image)");
+  if (!workspace) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: workspace is NULL");
+  if ((uintptr_t)workspace % 8) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: workspace must be 8-byte aligned");
+  if (workspace_bytes < ws_bytes) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: workspace is too small (curl_msssim_ragged_workspace_bytes)");
+  if (!on_grid(4, a_arena, b_arena, mask_arena)) return fail(CURL_E_SHAPE, "ragged batch: the arenas must be 4-byte aligned");
+  if (window_size < 1 || window_size > 2 * SSIM_R + 1 || (window_size & 1) == 0) return fail(CURL_E_KNOTS, "window_size must be odd and <= 11");
+
+  hipStream_t s = (hipStream_t)stream;
+  double* partial = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + partial_off);
+  const int* plan = static_cast<const int*>(plan_dev);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const unsigned long long hash = get64(p + MH_HASH), mb = mask_arena ? mask_bytes : 0;
+  SsimArgs win{};  // the window and the level: everything else travels beside it
+  win.levels = kMsLevels, win.radius = window_size / 2;
+  ssim_window(window_size, win.g);
+  unsigned pairs = 0;
+  for (int l = 0; l < kMsLevels; ++l) {
+    const unsigned grid = (unsigned)p[MH_GRID0 + l];
+    double* first = partial + 2 * (size_t)(unsigned)p[MH_PAIR0 + l];
+    win.level = l;
+    if (l == 0)
+      hipLaunchKernelGGL(msssim_ragged_bytes_kernel, dim3(grid), dim3(256), 0, s, win, plan, a_arena, b_arena, mask_arena, ws, first,
+                         (unsigned long long)a_bytes, (unsigned long long)b_bytes, mb, (unsigned long long)partial_off, hash, kMsStamp, B);
+    else
+      hipLaunchKernelGGL(msssim_ragged_level_kernel, dim3(grid), dim3(256), 0, s, win, plan, ws, first, (unsigned long long)partial_off, hash,
+                         kMsStamp, B);
+    pairs += grid;
+  }
+  hipLaunchKernelGGL(msssim_ragged_finish_kernel, dim3(B), dim3(256), 0, s, plan, (const double*)partial, stats, hash, kMsStamp, B, pairs);
+  return hip_done("curl_msssim_ragged_u8hwc");
+}
+
+}  // extern "C"

@@ -10,7 +10,10 @@ the foreground-aware ragged call (infer.enhance_many_foreground): the same files
 --gt_dir G scores every output against the target of the same stem in G (infer.enhance_and_score_many: the masked PSNR of
 the reference's Evaluator, exact on the bytes, one score call per batch): one `stem<TAB>psnr` line per image, then
 `mean<TAB>value<TAB>left_out` -- the mean over the images whose PSNR is finite and the number of images left out of it.
---scores_file F writes the same lines to F.
+--scores_file F writes the same lines to F.  --msssim (with --gt_dir) adds the reference's second figure, the MS-SSIM of the
+masked output against the masked target (infer.enhance_and_score_many_msssim, one more call per batch): the lines are
+`stem<TAB>psnr<TAB>msssim`, an image under 32 pixels on a side has msssim nan, and the last line is
+`mean<TAB>psnr mean<TAB>msssim mean<TAB>left_out of the psnr mean<TAB>left_out of the msssim mean`.
 """
 import argparse
 import math
@@ -19,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from .infer import build_net, enhance_and_score_many, enhance_many, enhance_many_foreground
+from .infer import build_net, enhance_and_score_many, enhance_and_score_many_msssim, enhance_many, enhance_many_foreground
 
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
@@ -56,9 +59,13 @@ def main(argv=None):
                         help="Folder of target images, matched to the images by file stem: print every output's masked PSNR "
                              "against its target and the mean over the finite ones")
     parser.add_argument("--scores_file", type=str, default=None, help="with --gt_dir: also write the score lines to this file")
+    parser.add_argument("--msssim", action="store_true",
+                        help="with --gt_dir: also print every output's MS-SSIM against its target (nan under 32 pixels on a side)")
     args = parser.parse_args(argv)
     if args.scores_file is not None and args.gt_dir is None:
         parser.error("--scores_file needs --gt_dir")
+    if args.msssim and args.gt_dir is None:
+        parser.error("--msssim needs --gt_dir")
     enhance = enhance_many_foreground if args.foreground_masks else enhance_many
     from PIL import Image
     images, masks = _by_stem(args.img_dir), _by_stem(args.mask_dir)
@@ -72,13 +79,23 @@ def main(argv=None):
     net = build_net(args.model_file, device, args.arch, args.polynomial_order)
     os.makedirs(args.out_dir, exist_ok=True)
     stems = list(images)
-    lines, finite = [], []
+    lines, finite, finite_ms = [], [], []
     for b0 in range(0, len(stems), args.batch_size):  # a batch of files in memory at a time
         batch = stems[b0:b0 + args.batch_size]
         imgs = [_rgb(images[stem]) for stem in batch]
         ms = [np.asarray(Image.open(masks[stem]).convert("L")) for stem in batch]
         if targets is None:
             outs = enhance(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)
+        elif args.msssim:
+            outs, psnr, msssim = enhance_and_score_many_msssim(net, imgs, ms, [_rgb(targets[stem]) for stem in batch], device,
+                                                               view=args.encoder_view, batch_size=args.batch_size,
+                                                               foreground=args.foreground_masks)
+            for stem, value, second in zip(batch, psnr, msssim):
+                lines.append(f"{stem}\t{float(value)!r}\t{float(second)!r}")
+                if math.isfinite(value):
+                    finite.append(float(value))
+                if math.isfinite(second):
+                    finite_ms.append(float(second))
         else:
             outs, psnr = enhance_and_score_many(net, imgs, ms, [_rgb(targets[stem]) for stem in batch], device, view=args.encoder_view,
                                                 batch_size=args.batch_size, foreground=args.foreground_masks)
@@ -90,7 +107,11 @@ def main(argv=None):
             Image.fromarray(out).save(os.path.join(args.out_dir, stem + ".png"))
     if targets is not None:
         mean = sum(finite) / len(finite) if finite else float("nan")
-        lines.append(f"mean\t{mean!r}\t{len(lines) - len(finite)}")
+        if args.msssim:
+            mean_ms = sum(finite_ms) / len(finite_ms) if finite_ms else float("nan")
+            lines.append(f"mean\t{mean!r}\t{mean_ms!r}\t{len(lines) - len(finite)}\t{len(lines) - len(finite_ms)}")
+        else:
+            lines.append(f"mean\t{mean!r}\t{len(lines) - len(finite)}")
         print("\n".join(lines))
         if args.scores_file is not None:
             with open(args.scores_file, "w") as f:

@@ -1377,6 +1377,103 @@ def psnr_u8hwc_ragged(a, b, masks=None):
     return 10.0 * torch.log10(255.0 ** 2 * 3.0 * sums[:, 1] / sums[:, 0])
 
 
+# ------------------------------------------------------------------ MS-SSIM of a ragged batch (include/curl_hip_ragged_msssim.h)
+_msssim_ragged_plans = {}  # (shapes, has_mask, device) -> _MsssimRaggedPlan
+MSSSIM_MIN_SIDE = 32       # metric.py:185-192 pools once more after the fifth level
+# metric.py:86: the five level weights, float32 there and raised to the images' dtype (here: float64)
+_MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+class _MsssimRaggedPlan:
+    """One MS-SSIM plan of the library's: the host copy (int32), its upload and what the callers read from it."""
+
+    def __init__(self, host, dev, ws_bytes):
+        self.host, self.dev, self.ws_bytes = host, dev, ws_bytes
+        w = host.numpy()
+        hw, dw = _lib.MSSSIM_RAGGED_HEADER_WORDS, _lib.MSSSIM_RAGGED_DESC_WORDS
+        B = int(w[1])
+        self.nbytes = host.numel() * 4
+        self.rgb_bytes, self.mask_bytes = (int(v) for v in w[12:16].view("int64"))
+        off = w[hw:hw + B * dw].reshape(B, dw)[:, 4:8].copy().view("int64")  # rgb_off, mask_off per descriptor (index order)
+        self.rgb_off, self.mask_off = ([int(v) for v in off[:, k]] for k in range(2))
+
+
+def _msssim_ragged_plan(shapes, has_mask, device):
+    """The MS-SSIM plan of a shape list, built on the host by the library, uploaded once and kept, as the op-0 plan is."""
+    key = (tuple(shapes), bool(has_mask), device)
+    plan = _msssim_ragged_plans.get(key)
+    if plan is None:
+        import numpy as np
+        lib = _lib.load()
+        B = len(shapes)
+        if B > _lib.RAGGED_MAX_IMAGES:
+            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
+        nbytes = lib.curl_msssim_ragged_plan_bytes(B)
+        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
+        hs, ws = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes]))
+        _lib.check(lib.curl_msssim_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, int(bool(has_mask)), host.data_ptr(), nbytes),
+                   "curl_msssim_ragged_plan")
+        if len(_msssim_ragged_plans) >= _RAGGED_PLANS_KEPT:
+            del _msssim_ragged_plans[next(iter(_msssim_ragged_plans))]
+        plan = _msssim_ragged_plans[key] = _MsssimRaggedPlan(host, host.to(device), lib.curl_msssim_ragged_workspace_bytes(host.data_ptr()))
+    return plan
+
+
+def msssim_stats_u8hwc_ragged(a, b, masks=None, window_size=11):
+    """The MS-SSIM statistics of two batches of byte images of different sizes, the whole batch in six launches
+    (curl_msssim_ragged_u8hwc): a and b a RaggedBytes or a list of uint8 [H,W,3] images of the same shape list (every side
+    >= 32), masks None or one uint8 [H,W] mask per image.  -> float64 [B,2,5] on the device: [i,0,l] the mean of level l's SSIM
+    map of image i, [i,1,l] that of its contrast-structure map -- msssim_stats of bytes / 255 times (mask != 0), without the
+    float images.  The same bits on every call, for an image alone or in any company and order."""
+    shapes = _score_shapes(a, "a")
+    if _score_shapes(b, "b") != shapes:
+        raise ValueError(f"a and b must hold images of the same sizes, got {shapes} and {_score_shapes(b, 'b')}")
+    _score_masks(masks, shapes)
+    if window_size not in (1, 3, 5, 7, 9, 11):
+        raise ValueError(f"window_size must be odd and 1..11, got {window_size}")
+    for k, (h, w) in enumerate(shapes):
+        if h < MSSSIM_MIN_SIDE or w < MSSSIM_MIN_SIDE:
+            raise ValueError(f"image {k} is {h}x{w}: MS-SSIM needs H, W >= {MSSSIM_MIN_SIDE} (five pyramid levels, each followed by a 2x2 pooling)")
+    if not shapes:
+        device = next((x.device for x in (a, b) if isinstance(x, RaggedBytes)), None)
+        return torch.zeros((0, 2, 5), dtype=torch.float64, device=device)
+    lib = _lib.load()
+    ra, wm = _ragged_inputs(a, masks, None)
+    rb = b if isinstance(b, RaggedBytes) else RaggedBytes.pack(list(b), ra.device)
+    _need_device(rb.arena, "b")
+    _check_same_device([("a", ra.arena), ("b", rb.arena)])
+    B = len(ra)
+    plan = _msssim_ragged_plan(ra.shapes, wm is not None, ra.device)
+    if ra.offsets != plan.rgb_off or rb.offsets != plan.rgb_off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    stats = torch.empty((B, 2, 5), dtype=torch.float64, device=ra.device)
+    ws = torch.empty(plan.ws_bytes // 8, dtype=torch.float64, device=ra.device)
+    with torch.cuda.device(ra.device):
+        rc = lib.curl_msssim_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
+                                          _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
+                                          stats.data_ptr(), stats.numel() * 8, ws.data_ptr(), plan.ws_bytes, plan.host.data_ptr(),
+                                          plan.dev.data_ptr(), plan.nbytes, window_size, 0, _stream(ra.arena))
+    _lib.check(rc, "curl_msssim_ragged_u8hwc")
+    return stats
+
+
+def msssim_from_stats(stats):
+    """metric.py:200-207 on [B,2,5] statistics, in their dtype on their device: (x + 1) / 2, the powers by the five weights,
+    prod(mcs[:-1]^w[:-1] * ssims[-1]^w[-1]) -- the reference's quirk kept: the last factor enters four times."""
+    w = torch.tensor(_MSSSIM_WEIGHTS, dtype=torch.float32).to(device=stats.device, dtype=stats.dtype)
+    x = (stats + 1) / 2
+    pow1, pow2 = x[:, 1] ** w, x[:, 0] ** w
+    return torch.prod(pow1[:, :-1] * pow2[:, -1].reshape(-1, 1), dim=1)
+
+
+def msssim_u8hwc_ragged(a, b, masks=None, window_size=11):
+    """The MS-SSIM of every image of a ragged byte batch against its target, float64 [B] on the device: metric.py:200-207 on
+    msssim_stats_u8hwc_ragged's statistics, in float64, without a synchronisation."""
+    return msssim_from_stats(msssim_stats_u8hwc_ragged(a, b, masks, window_size))
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
