@@ -177,6 +177,19 @@ SIGNATURES_RAGGED_MSSSIM = {
 MSSSIM_RAGGED_STAMP, MSSSIM_RAGGED_HEADER_WORDS, MSSSIM_RAGGED_DESC_WORDS, MSSSIM_RAGGED_LEVEL_WORD, MSSSIM_RAGGED_LEVEL_WORDS = \
     0x4D535231, 32, 64, 16, 8
 
+# include/curl_hip_ragged_loss.h: the CURLLoss statistics of a ragged byte batch (a tenth table, for the same reason; the
+# argument lists are the MS-SSIM entries')
+SIGNATURES_RAGGED_LOSS = {
+    "curl_loss_ragged_plan_bytes": (_sz, [_i]),
+    "curl_loss_ragged_plan": (_i, [_i, _c_f, _c_f, _i, _c_f, _sz]),
+    "curl_loss_ragged_workspace_bytes": (_sz, [_c_f]),
+    "curl_loss_ragged_u8hwc": (_i, [_c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _sz, _c_f, _c_f, _sz, _i, _u, _c_f]),
+}
+# the plan's layout (int32 words): CURL_LOSS_RAGGED_STAMP, _OP, _HEADER_WORDS, _DESC_WORDS, _LEVEL_WORD, _LEVEL_WORDS,
+# _TERMS_WORD, _TERMS
+LOSS_RAGGED_STAMP, LOSS_RAGGED_OP, LOSS_RAGGED_HEADER_WORDS, LOSS_RAGGED_DESC_WORDS, LOSS_RAGGED_LEVEL_WORD, \
+    LOSS_RAGGED_LEVEL_WORDS, LOSS_RAGGED_TERMS_WORD, LOSS_RAGGED_TERMS = 0x4C535231, 6, 32, 64, 16, 8, 28, 5
+
 _lib = None
 
 
@@ -201,7 +214,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GRAD.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_FG.items()) + list(SIGNATURES_RAGGED.items()) + list(SIGNATURES_VIEW_RAGGED.items()) + \
-            list(SIGNATURES_RAGGED_FG.items()) + list(SIGNATURES_RAGGED_SCORE.items()) + list(SIGNATURES_RAGGED_MSSSIM.items()):
+            list(SIGNATURES_RAGGED_FG.items()) + list(SIGNATURES_RAGGED_SCORE.items()) + list(SIGNATURES_RAGGED_MSSSIM.items()) + \
+            list(SIGNATURES_RAGGED_LOSS.items()):
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -18,11 +18,12 @@ INCLUDE_VIEW_RAGGED = os.path.join(os.path.dirname(HERE), "include", "curl_hip_v
 INCLUDE_RAGGED_FG = os.path.join(os.path.dirname(HERE), "include", "curl_hip_ragged_fg.h")
 INCLUDE_RAGGED_SCORE = os.path.join(os.path.dirname(HERE), "include", "curl_hip_ragged_score.h")
 INCLUDE_RAGGED_MSSSIM = os.path.join(os.path.dirname(HERE), "include", "curl_hip_ragged_msssim.h")
+INCLUDE_RAGGED_LOSS = os.path.join(os.path.dirname(HERE), "include", "curl_hip_ragged_loss.h")
 
 
 def _deps():
     """Everything the one translation unit reads: csrc/*.h|.hip|.inc, csrc/kernels/*.inc, the public header."""
-    out = [INCLUDE, INCLUDE_GRAD, INCLUDE_VIEW, INCLUDE_FG, INCLUDE_RAGGED, INCLUDE_VIEW_RAGGED, INCLUDE_RAGGED_FG, INCLUDE_RAGGED_SCORE, INCLUDE_RAGGED_MSSSIM, os.path.abspath(__file__)]  # this file too: a change of FLAGS rebuilds
+    out = [INCLUDE, INCLUDE_GRAD, INCLUDE_VIEW, INCLUDE_FG, INCLUDE_RAGGED, INCLUDE_VIEW_RAGGED, INCLUDE_RAGGED_FG, INCLUDE_RAGGED_SCORE, INCLUDE_RAGGED_MSSSIM, INCLUDE_RAGGED_LOSS, os.path.abspath(__file__)]  # this file too: a change of FLAGS rebuilds
     for d, _, files in os.walk(os.path.join(HERE, "csrc")):
         out += [os.path.join(d, f) for f in files if f.endswith((".h", ".hip", ".inc"))]
     return out

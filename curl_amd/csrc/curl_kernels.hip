@@ -27,6 +27,7 @@
 #include "../../include/curl_hip_ragged_fg.h"
 #include "../../include/curl_hip_ragged_score.h"
 #include "../../include/curl_hip_ragged_msssim.h"
+#include "../../include/curl_hip_ragged_loss.h"
 #include "curl_math_bwd.h"
 #include "curl_math_poly.h"
 #include "curl_math_loss.h"
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/stream_ragged_fg.inc"
 #include "kernels/score_ragged.inc"
 #include "kernels/msssim_ragged.inc"
+#include "kernels/loss_ragged.inc"
 #include "kernels/encoder_view_ragged.inc"
 #include "kernels/host_api.inc"
 #include "kernels/host_api_grad.inc"
@@ -237,4 +239,5 @@ __global__ __launch_bounds__(256) void knots_prep_kernel(PrepArgs a) { prep_imag
 #include "kernels/host_api_ragged_fg.inc"
 #include "kernels/host_api_ragged_score.inc"
 #include "kernels/host_api_ragged_msssim.inc"
+#include "kernels/host_api_ragged_loss.inc"
 #include "kernels/host_api_view.inc"

@@ -749,7 +749,8 @@ extern "C" {
 // 0.1.18: the ragged byte entries, foreground-aware: dead wavefronts store white unread (include/curl_hip_ragged_fg.h)
 // 0.1.19: the exact score of a ragged byte batch: per-image integer SSE and pixel count (include/curl_hip_ragged_score.h)
 // 0.1.20: the MS-SSIM statistics of a ragged byte batch: six launches from the bytes (include/curl_hip_ragged_msssim.h)
-int curl_version(void) { return 120; }
+// 0.1.21: the CURLLoss statistics of a ragged byte batch: six launches from the bytes (include/curl_hip_ragged_loss.h)
+int curl_version(void) { return 121; }
 
 const char* curl_last_error(void) { return g_err; }
 

@@ -6,15 +6,26 @@
 // ------------------------------------------------------------------------------------------------
 static size_t ms_plan_words(int B) { return kMsHeaderWords + (size_t)B * kMsDescWords; }
 
-static int ms_build(int B, const int* H, const int* W, bool has_mask, int* p) {
+// The two plans of this layout: the MS-SSIM statistics' and the CURLLoss statistics' (include/curl_hip_ragged_loss.h,
+// host_api_ragged_loss.inc), which walks the same pyramid on one channel and adds the level-0 workgroups' term sums.
+struct MsPlanKind {
+  unsigned stamp, op;
+  unsigned planes;  // float planes per pyramid level: a's three and b's / prediction L and target L
+  unsigned terms;   // float64 per level-0 workgroup behind the pairs (their byte offset: header word LH_TERMS_OFF, loss_ragged.inc)
+  const char* what;
+  const char* plan_fn;
+};
+static const MsPlanKind kMsPlan{kMsStamp, kMsOp, 6u, 0u, "ragged MS-SSIM", "curl_msssim_ragged_plan"};
+
+static int ms_build(const MsPlanKind& kind, int B, const int* H, const int* W, bool has_mask, int* p) {
   uint64_t hash = 1469598103934665603ull;
-  hash = ragged_hash_word(ragged_hash_word(ragged_hash_word(hash, kMsStamp), has_mask), (uint32_t)B);
+  hash = ragged_hash_word(ragged_hash_word(ragged_hash_word(hash, kind.stamp), has_mask), (uint32_t)B);
   for (int i = 0; i < B; ++i) {
     if (H[i] <= 0 || W[i] <= 0) return fail(CURL_E_SHAPE, "ragged batch: every H and W must be positive");
     if ((uint64_t)H[i] * (uint64_t)W[i] > (1ull << 30)) return fail(CURL_E_SHAPE, "ragged batch: an image's H*W exceeds 2^30 pixels");
     if ((H[i] >> MSSSIM_LEVELS) < 1 || (W[i] >> MSSSIM_LEVELS) < 1) {  // metric.py:185-192 pools once more after the fifth level
-      snprintf(g_err, sizeof(g_err), "ragged MS-SSIM: image %d is %dx%d; MS-SSIM needs H, W >= 32 (five pyramid levels, each followed by a 2x2 pooling)",
-               i, H[i], W[i]);
+      snprintf(g_err, sizeof(g_err), "%s: image %d is %dx%d; MS-SSIM needs H, W >= 32 (five pyramid levels, each followed by a 2x2 pooling)",
+               kind.what, i, H[i], W[i]);
       return CURL_E_SHAPE;
     }
     hash = ragged_hash_word(ragged_hash_word(hash, (uint32_t)H[i]), (uint32_t)W[i]);
@@ -39,7 +50,7 @@ static int ms_build(int B, const int* H, const int* W, bool has_mask, int* p) {
       if (l >= 1) {
         planes = align(planes);
         put64(v + ML_PLANES, planes);
-        planes += 6ull * sizeof(float) * (uint64_t)h * (uint64_t)w;
+        planes += (uint64_t)kind.planes * sizeof(float) * (uint64_t)h * (uint64_t)w;
       }
     }
   }
@@ -52,26 +63,33 @@ static int ms_build(int B, const int* H, const int* W, bool has_mask, int* p) {
       v[ML_PAIR] = (int)(pair0[l] + (uint64_t)v[ML_FIRST]);
     }
   planes = align(planes);
-  p[MH_STAMP] = (int)kMsStamp, p[MH_B] = B, p[MH_OP] = (int)kMsOp, p[MH_HAS_MASK] = has_mask, p[MH_LAUNCHES] = kMsLevels + 1;
+  p[MH_STAMP] = (int)kind.stamp, p[MH_B] = B, p[MH_OP] = (int)kind.op, p[MH_HAS_MASK] = has_mask, p[MH_LAUNCHES] = kMsLevels + 1;
   for (int l = 0; l < kMsLevels; ++l) p[MH_GRID0 + l] = (int)grid[l], p[MH_PAIR0 + l] = (int)pair0[l];
   put64(p + MH_RGB_BYTES, arenas.out), put64(p + MH_MASK_BYTES, arenas.mask), put64(p + MH_HASH, hash);
-  put64(p + MH_PARTIAL_OFF, planes), put64(p + MH_WS_BYTES, planes + pairs * 2 * sizeof(double));
+  const uint64_t terms_off = planes + pairs * 2 * sizeof(double);
+  put64(p + MH_PARTIAL_OFF, planes), put64(p + MH_WS_BYTES, terms_off + grid[0] * kind.terms * sizeof(double));
+  if (kind.terms) put64(p + LH_TERMS_OFF, terms_off);
   return 0;
 }
 
 // A host plan is the caller's memory: what the entries read from it is checked for being a plan's
-static int ms_host_plan(const void* host_plan) {
+static int ms_host_plan(const MsPlanKind& kind, const void* host_plan) {
   if (!host_plan) return fail(CURL_E_NULL, "host_plan is NULL");
   if ((uintptr_t)host_plan % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the host plan must be 8-byte aligned");
   const int* p = static_cast<const int*>(host_plan);
-  bool ok = (unsigned)p[MH_STAMP] == kMsStamp && p[MH_B] >= 1 && p[MH_B] <= kRaggedMaxImages;
+  bool ok = (unsigned)p[MH_STAMP] == kind.stamp && p[MH_B] >= 1 && p[MH_B] <= kRaggedMaxImages;
   uint64_t pairs = 0;
   for (int l = 0; ok && l < kMsLevels; ++l) {
     ok = p[MH_GRID0 + l] >= p[MH_B] && (uint64_t)(unsigned)p[MH_PAIR0 + l] == pairs;
     pairs += (uint64_t)(unsigned)p[MH_GRID0 + l];
   }
-  ok = ok && get64(p + MH_PARTIAL_OFF) % 8 == 0 && get64(p + MH_WS_BYTES) == get64(p + MH_PARTIAL_OFF) + pairs * 2 * sizeof(double);
-  if (!ok) return fail(CURL_E_WORKSPACE, "ragged MS-SSIM: host_plan holds no plan (curl_msssim_ragged_plan)");
+  const uint64_t terms_off = get64(p + MH_PARTIAL_OFF) + pairs * 2 * sizeof(double);
+  ok = ok && get64(p + MH_PARTIAL_OFF) % 8 == 0 && (!kind.terms || get64(p + LH_TERMS_OFF) == terms_off) &&
+       get64(p + MH_WS_BYTES) == terms_off + (uint64_t)(unsigned)p[MH_GRID0] * kind.terms * sizeof(double);
+  if (!ok) {
+    snprintf(g_err, sizeof(g_err), "%s: host_plan holds no plan (%s)", kind.what, kind.plan_fn);
+    return CURL_E_WORKSPACE;
+  }
   return 0;
 }
 
@@ -91,11 +109,11 @@ int curl_msssim_ragged_plan(int B, const int* H, const int* W, int has_mask, voi
   if ((uintptr_t)host_buf % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer must be 8-byte aligned");
   if (bytes < ms_plan_words(B) * sizeof(int))
     return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer is too small (curl_msssim_ragged_plan_bytes)");
-  return ms_build(B, H, W, has_mask != 0, static_cast<int*>(host_buf));
+  return ms_build(kMsPlan, B, H, W, has_mask != 0, static_cast<int*>(host_buf));
 }
 
 size_t curl_msssim_ragged_workspace_bytes(const void* host_plan) {
-  const int rc = ms_host_plan(host_plan);
+  const int rc = ms_host_plan(kMsPlan, host_plan);
   g_err[0] = 0;
   if (rc || static_cast<const int*>(host_plan)[MH_OP] != (int)kMsOp) return 0;
   return (size_t)get64(static_cast<const int*>(host_plan) + MH_WS_BYTES);
@@ -109,7 +127,7 @@ int curl_msssim_ragged_u8hwc(const uint8_t* a_arena, size_t a_bytes, const uint8
   // check_ragged's checks in its order and wording, on this header's plan; then this entry's own
   if (!a_arena || !b_arena) return fail(CURL_E_NULL, "arena pointer is NULL");
   if (!plan_dev) return fail(CURL_E_NULL, "plan_dev is NULL");
-  if (int rc = ms_host_plan(host_plan)) return rc;
+  if (int rc = ms_host_plan(kMsPlan, host_plan)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (flags must be 0)");
   const int* p = static_cast<const int*>(host_plan);
   if (p[MH_OP] != (int)kMsOp) return fail(CURL_E_WORKSPACE, "ragged batch: the plan was made for another operator");

@@ -157,7 +157,7 @@ def enhance_and_score_many(net, images_u8, masks_u8, targets_u8, device, view="p
     as the metric's mask, exact on the bytes (ops.psnr_u8hwc_ragged): nan where the mask keeps no pixel, inf for an output
     equal to its target.  Per batch the out arena stays on the device, the targets go up as one RGB arena, the mask arena is
     the one already uploaded, and the score is ONE call; no float image is made."""
-    results, psnr, _ = _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim=False)
+    results, psnr, _, _ = _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim=False)
     return results, psnr
 
 
@@ -168,11 +168,23 @@ def enhance_and_score_many_msssim(net, images_u8, masks_u8, targets_u8, device, 
     (ops.msssim_u8hwc_ragged): per batch ONE more call, on the out arena, the target arena and the mask arena the PSNR call
     uses.  An image under 32 pixels on a side has no five-level pyramid: it gets nan and is left out of the call (the rest of
     its batch is then packed again on the device)."""
-    return _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim=True)
+    return _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim=True)[:3]
 
 
-def _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim):
-    """The body of the two functions above -> (outputs, psnr, msssim or None)."""
+@torch.no_grad()
+def enhance_and_evaluate_many(net, images_u8, masks_u8, targets_u8, device, view="pil", batch_size=32, foreground=False):
+    """enhance_and_score_many_msssim with the reference Evaluator's first figure (evaluate.py:101): -> (outputs, psnr, msssim,
+    loss).  loss is a float64 numpy array [N], the criterion of every output against its target under its mask -- CURLLoss
+    (model.py:78-116) image by image, as CURLLoss()(pred[None], target[None], mask[None]) -- from the bytes
+    (ops.curl_loss_u8hwc_ragged): per batch ONE more call, on the arenas the other two scores use.  It is the criterion of the
+    BYTES WRITTEN (byte / 255), not of the network's unrounded float output, which the training loop's Evaluator sees.  An
+    image under 32 pixels on a side gets nan and is left out of the call, as for msssim; an image whose mask keeps no pixel
+    gets nan too (the reference's 0 / 0).  Outputs, psnr and msssim are enhance_and_score_many_msssim's."""
+    return _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim=True, loss=True)
+
+
+def _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch_size, foreground, msssim, loss=False):
+    """The body of the three functions above -> (outputs, psnr, msssim or None, loss or None)."""
     if len(targets_u8) != len(images_u8):
         raise ValueError(f"one target per image: {len(images_u8)} images, {len(targets_u8)} targets")
     targets = []
@@ -183,30 +195,32 @@ def _enhance_and_score(net, images_u8, masks_u8, targets_u8, device, view, batch
         if t.shape[:2] != np.asarray(img).shape[:2]:
             raise ValueError(f"target {i} is {t.shape[0]}x{t.shape[1]}, its image {np.asarray(img).shape[0]}x{np.asarray(img).shape[1]}")
         targets.append(t)
-    results, scores, ms = [], [], []
+    results, scores, ms, losses = [], [], [], []
     for k, (rb, wm) in enumerate(_packed_batches(images_u8, masks_u8, device, view, batch_size)):
         small, msmall = _encoder_views(rb, wm, view)
         out = _full_resolution_device(net, rb, wm, small, msmall, foreground)
         tg = ops.RaggedBytes.pack([np.ascontiguousarray(t[..., :3]) for t in targets[k * batch_size:(k + 1) * batch_size]], rb.device)
         psnr = ops.psnr_u8hwc_ragged(out, tg, wm)  # one score call per batch, on the arenas the batch already has
         if msssim:
-            ms.append(_msssim_of_batch(out, tg, wm))
+            ms.append(_pyramid_score_of_batch(ops.msssim_u8hwc_ragged, out, tg, wm))
+        if loss:
+            losses.append(_pyramid_score_of_batch(ops.curl_loss_u8hwc_ragged, out, tg, wm))
         results += _download(out)
         scores.append(psnr.cpu().numpy())
     cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.float64)  # noqa: E731
-    return results, cat(scores), cat(ms) if msssim else None
+    return results, cat(scores), cat(ms) if msssim else None, cat(losses) if loss else None
 
 
-def _msssim_of_batch(out, tg, wm):
-    """The MS-SSIM of a batch's out arena against its target arena under its mask arena, one call -> float64 numpy [n]; nan
-    for the images under 32 pixels on a side, which the call never sees."""
+def _pyramid_score_of_batch(score, out, tg, wm):
+    """A five-level score (ops.msssim_u8hwc_ragged, ops.curl_loss_u8hwc_ragged) of a batch's out arena against its target arena
+    under its mask arena, one call -> float64 numpy [n]; nan for the images under 32 pixels on a side, which the call never sees."""
     keep = [i for i, (h, w) in enumerate(out.shapes) if min(h, w) >= ops.MSSSIM_MIN_SIDE]
     values = np.full(len(out), np.nan, dtype=np.float64)
     if len(keep) == len(out):
-        values[:] = ops.msssim_u8hwc_ragged(out, tg, wm).cpu().numpy()
+        values[:] = score(out, tg, wm).cpu().numpy()
     elif keep:
         sub = [ops.RaggedBytes.pack([x.image(i) for i in keep], out.device) for x in (out, tg, wm)]
-        values[keep] = ops.msssim_u8hwc_ragged(*sub).cpu().numpy()
+        values[keep] = score(*sub).cpu().numpy()
     return values
 
 

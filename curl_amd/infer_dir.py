@@ -13,7 +13,12 @@ the reference's Evaluator, exact on the bytes, one score call per batch): one `s
 --scores_file F writes the same lines to F.  --msssim (with --gt_dir) adds the reference's second figure, the MS-SSIM of the
 masked output against the masked target (infer.enhance_and_score_many_msssim, one more call per batch): the lines are
 `stem<TAB>psnr<TAB>msssim`, an image under 32 pixels on a side has msssim nan, and the last line is
-`mean<TAB>psnr mean<TAB>msssim mean<TAB>left_out of the psnr mean<TAB>left_out of the msssim mean`.
+`mean<TAB>psnr mean<TAB>msssim mean<TAB>left_out of the psnr mean<TAB>left_out of the msssim mean`.  --loss (with --gt_dir,
+combinable with --msssim) appends the Evaluator's first figure, the criterion (CURLLoss, image by image) of the output FILE's
+pixels -- byte / 255, not the network's unrounded float output -- against the target under the mask
+(infer.enhance_and_evaluate_many, one more call per batch): a last `loss` column on every image's line (nan under 32 pixels
+on a side or where the mask keeps no pixel), and on the last line its mean over the finite ones behind the other means and
+its left_out count behind the other counts.
 """
 import argparse
 import math
@@ -22,7 +27,8 @@ import os
 import numpy as np
 import torch
 
-from .infer import build_net, enhance_and_score_many, enhance_and_score_many_msssim, enhance_many, enhance_many_foreground
+from .infer import (build_net, enhance_and_evaluate_many, enhance_and_score_many, enhance_and_score_many_msssim, enhance_many,
+                    enhance_many_foreground)
 
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
 
@@ -61,7 +67,12 @@ def main(argv=None):
     parser.add_argument("--scores_file", type=str, default=None, help="with --gt_dir: also write the score lines to this file")
     parser.add_argument("--msssim", action="store_true",
                         help="with --gt_dir: also print every output's MS-SSIM against its target (nan under 32 pixels on a side)")
+    parser.add_argument("--loss", action="store_true",
+                        help="with --gt_dir: also print the criterion (CURLLoss) of every output file's pixels against its target "
+                             "(nan under 32 pixels on a side)")
     args = parser.parse_args(argv)
+    if args.loss and args.gt_dir is None:
+        parser.error("--loss needs --gt_dir")
     if args.scores_file is not None and args.gt_dir is None:
         parser.error("--scores_file needs --gt_dir")
     if args.msssim and args.gt_dir is None:
@@ -79,13 +90,22 @@ def main(argv=None):
     net = build_net(args.model_file, device, args.arch, args.polynomial_order)
     os.makedirs(args.out_dir, exist_ok=True)
     stems = list(images)
-    lines, finite, finite_ms = [], [], []
+    lines, finite, finite_ms, finite_loss = [], [], [], []
     for b0 in range(0, len(stems), args.batch_size):  # a batch of files in memory at a time
         batch = stems[b0:b0 + args.batch_size]
         imgs = [_rgb(images[stem]) for stem in batch]
         ms = [np.asarray(Image.open(masks[stem]).convert("L")) for stem in batch]
         if targets is None:
             outs = enhance(net, imgs, ms, device, view=args.encoder_view, batch_size=args.batch_size)
+        elif args.loss:
+            outs, psnr, msssim, loss = enhance_and_evaluate_many(net, imgs, ms, [_rgb(targets[stem]) for stem in batch], device,
+                                                                 view=args.encoder_view, batch_size=args.batch_size,
+                                                                 foreground=args.foreground_masks)
+            for stem, value, second, third in zip(batch, psnr, msssim, loss):
+                lines.append(f"{stem}\t{float(value)!r}" + (f"\t{float(second)!r}" if args.msssim else "") + f"\t{float(third)!r}")
+                for figure, kept in ((value, finite), (second, finite_ms), (third, finite_loss)):
+                    if math.isfinite(figure):
+                        kept.append(float(figure))
         elif args.msssim:
             outs, psnr, msssim = enhance_and_score_many_msssim(net, imgs, ms, [_rgb(targets[stem]) for stem in batch], device,
                                                                view=args.encoder_view, batch_size=args.batch_size,
@@ -107,7 +127,11 @@ def main(argv=None):
             Image.fromarray(out).save(os.path.join(args.out_dir, stem + ".png"))
     if targets is not None:
         mean = sum(finite) / len(finite) if finite else float("nan")
-        if args.msssim:
+        if args.loss:
+            kept = [finite] + ([finite_ms] if args.msssim else []) + [finite_loss]
+            means = [sum(k) / len(k) if k else float("nan") for k in kept]
+            lines.append("mean\t" + "\t".join(repr(v) for v in means) + "\t" + "\t".join(str(len(lines) - len(k)) for k in kept))
+        elif args.msssim:
             mean_ms = sum(finite_ms) / len(finite_ms) if finite_ms else float("nan")
             lines.append(f"mean\t{mean!r}\t{mean_ms!r}\t{len(lines) - len(finite)}\t{len(lines) - len(finite_ms)}")
         else:

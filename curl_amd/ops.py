@@ -1474,6 +1474,97 @@ def msssim_u8hwc_ragged(a, b, masks=None, window_size=11):
     return msssim_from_stats(msssim_stats_u8hwc_ragged(a, b, masks, window_size))
 
 
+# ------------------------------------------------------------------ CURLLoss of a ragged batch (include/curl_hip_ragged_loss.h)
+_loss_ragged_plans = {}  # (shapes, has_mask, device) -> _MsssimRaggedPlan (the layout is the MS-SSIM plan's)
+
+
+def _loss_ragged_plan(shapes, has_mask, device):
+    """The loss plan of a shape list, built on the host by the library, uploaded once and kept, as the MS-SSIM plan is."""
+    key = (tuple(shapes), bool(has_mask), device)
+    plan = _loss_ragged_plans.get(key)
+    if plan is None:
+        import numpy as np
+        lib = _lib.load()
+        B = len(shapes)
+        if B > _lib.RAGGED_MAX_IMAGES:
+            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
+        nbytes = lib.curl_loss_ragged_plan_bytes(B)
+        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
+        hs, ws = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes]))
+        _lib.check(lib.curl_loss_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, int(bool(has_mask)), host.data_ptr(), nbytes),
+                   "curl_loss_ragged_plan")
+        if len(_loss_ragged_plans) >= _RAGGED_PLANS_KEPT:
+            del _loss_ragged_plans[next(iter(_loss_ragged_plans))]
+        plan = _loss_ragged_plans[key] = _MsssimRaggedPlan(host, host.to(device), lib.curl_loss_ragged_workspace_bytes(host.data_ptr()))
+    return plan
+
+
+def loss_stats_u8hwc_ragged(pred, target, masks=None, window_size=11):
+    """The statistics of the reference's CURLLoss (model.py:78-116) of two batches of byte images of different sizes, the whole
+    batch in six launches (curl_loss_ragged_u8hwc): pred and target a RaggedBytes or a list of uint8 [H,W,3] images of the same
+    shape list (every side >= 32), masks None or one uint8 [H,W] mask per image.  -> float64 [B,3,5] on the device: [i,0] the
+    raw sums over the pixels whose mask byte is not 0 of |p - t|, the cosine similarity, |Lab_p - Lab_t| and |cone_p - cone_t|,
+    then their number N; [i,1,l] / [i,2,l] the means of level l's SSIM and contrast-structure maps of the clamped-L planes.
+    The prediction is the BYTES / 255 -- an output file's pixels, not a network's unrounded float output.  The same bits on every
+    call, for an image alone or in any company and order."""
+    shapes = _score_shapes(pred, "pred")
+    if _score_shapes(target, "target") != shapes:
+        raise ValueError(f"pred and target must hold images of the same sizes, got {shapes} and {_score_shapes(target, 'target')}")
+    _score_masks(masks, shapes)
+    if window_size not in (1, 3, 5, 7, 9, 11):
+        raise ValueError(f"window_size must be odd and 1..11, got {window_size}")
+    for k, (h, w) in enumerate(shapes):
+        if h < MSSSIM_MIN_SIDE or w < MSSSIM_MIN_SIDE:
+            raise ValueError(f"image {k} is {h}x{w}: the loss's MS-SSIM term needs H, W >= {MSSSIM_MIN_SIDE} (five pyramid levels, each followed by a 2x2 pooling)")
+    if not shapes:
+        device = next((x.device for x in (pred, target) if isinstance(x, RaggedBytes)), None)
+        return torch.zeros((0, 3, 5), dtype=torch.float64, device=device)
+    lib = _lib.load()
+    ra, wm = _ragged_inputs(pred, masks, None)
+    rb = target if isinstance(target, RaggedBytes) else RaggedBytes.pack(list(target), ra.device)
+    _need_device(rb.arena, "target")
+    _check_same_device([("pred", ra.arena), ("target", rb.arena)])
+    B = len(ra)
+    plan = _loss_ragged_plan(ra.shapes, wm is not None, ra.device)
+    if ra.offsets != plan.rgb_off or rb.offsets != plan.rgb_off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    stats = torch.empty((B, 3, 5), dtype=torch.float64, device=ra.device)
+    ws = torch.empty(plan.ws_bytes // 8, dtype=torch.float64, device=ra.device)
+    with torch.cuda.device(ra.device):
+        rc = lib.curl_loss_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
+                                        _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
+                                        stats.data_ptr(), stats.numel() * 8, ws.data_ptr(), plan.ws_bytes, plan.host.data_ptr(),
+                                        plan.dev.data_ptr(), plan.nbytes, window_size, 0, _stream(ra.arena))
+    _lib.check(rc, "curl_loss_ragged_u8hwc")
+    return stats
+
+
+def curl_loss_from_stats(stats, shapes):
+    """model.py:89-116 on [B,3,5] statistics and the images' [(H, W)], in float64 on the statistics' device (a CPU tensor too; no
+    synchronisation) -> float64 [B], every image's loss as CURLLoss()(pred[None], target[None], mask[None]) gives it: rgb, lab,
+    hsv = S / (3 N); cosine = 1 - (S_cos + (H W - N)) / (H W) -- a masked-out pixel has a cosine similarity of 0 and the mean runs
+    over all pixels --; ssim = 1 - msssim_from_stats(rows 1, 2); loss = (rgb + cosine + lab + hsv + 10 ssim) / 5.  N = 0 gives
+    nan, as the reference's 0 / 0 does."""
+    stats = stats.to(torch.float64)
+    if stats.dim() != 3 or tuple(stats.shape[1:]) != (3, 5) or stats.shape[0] != len(shapes):
+        raise ValueError(f"stats must be [B,3,5] with one (H, W) per image, got {tuple(stats.shape)} and {len(shapes)} shapes")
+    hw = torch.tensor([float(h * w) for h, w in shapes], dtype=torch.float64).to(stats.device)
+    S, n = stats[:, 0, :4], stats[:, 0, 4]
+    rgb, lab, hsv = (S[:, k] / (3.0 * n) for k in (0, 2, 3))
+    cosine = 1.0 - (S[:, 1] + (hw - n)) / hw
+    ssim = 1.0 - msssim_from_stats(stats[:, 1:])
+    return (rgb + cosine + lab + hsv + 10.0 * ssim) / 5.0
+
+
+def curl_loss_u8hwc_ragged(pred, target, masks=None):
+    """The reference's CURLLoss of every image of a ragged byte batch against its target, float64 [B] on the device:
+    curl_loss_from_stats on loss_stats_u8hwc_ragged's statistics.  It is the criterion of the bytes written (byte / 255)."""
+    stats = loss_stats_u8hwc_ragged(pred, target, masks)
+    return curl_loss_from_stats(stats, _score_shapes(pred, "pred"))
+
+
 _view_plans = {}  # (H, W, size, device) -> the uploaded plan (int32, a few dozen KB each)
 _VIEW_PLANS_KEPT = 16
 
