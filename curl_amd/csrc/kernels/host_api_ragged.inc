@@ -20,6 +20,8 @@ static int ragged_op(int num_coeffs_or_0, RaggedOp& op) {
   return 0;
 }
 static size_t ragged_plan_words(int B) { return kRaggedHeaderWords + (size_t)B * kRaggedDescWords; }
+template <class... A>  // fail() with a message that names one of the family's functions or arenas
+static int ragged_failf(int code, const char* fmt, A... a) { return snprintf(g_err, sizeof(g_err), fmt, a...), code; }
 static void put64(int* p, uint64_t v) { p[0] = (int)(uint32_t)v, p[1] = (int)(uint32_t)(v >> 32); }
 static uint64_t get64(const int* p) { return (uint64_t)(uint32_t)p[0] | ((uint64_t)(uint32_t)p[1] << 32); }
 static uint64_t ragged_hash_word(uint64_t h, uint32_t w) {  // FNV-1a, a byte at a time
@@ -28,11 +30,11 @@ static uint64_t ragged_hash_word(uint64_t h, uint32_t w) {  // FNV-1a, a byte at
 }
 // The arenas' layout, the one rule of every plan over a ragged batch (this file's and the encoder view's, host_api_view.inc):
 // the images in index order, each offset rounded up to kRaggedAlign.  place() gives image i its three offsets and moves on;
-// afterwards img / mask / out are the arena sizes.
+// afterwards img / mask / out are the arena sizes.  align() is the rounding, for whatever else a plan lays out by the rule.
 struct RaggedArenas {
   uint64_t img = 0, mask = 0, out = 0;
+  static uint64_t align(uint64_t v) { return (v + kRaggedAlign - 1) & ~(kRaggedAlign - 1); }
   int place(uint64_t px, int channels, bool has_mask, uint64_t& img_off, uint64_t& mask_off, uint64_t& out_off) {
-    const auto align = [](uint64_t v) { return (v + kRaggedAlign - 1) & ~(kRaggedAlign - 1); };
     img = align(img), out = align(out), mask = align(mask);
     img_off = img, out_off = out, mask_off = has_mask ? mask : 0;
     img += px * (uint64_t)channels, out += px * 3u, mask += has_mask ? px : 0;
@@ -66,13 +68,33 @@ static unsigned ragged_row_threads(int B, const int* H, const int* W, const Ragg
   return best_t;
 }
 
+// What every plan builder of the family asks of its arguments before it reads a size, in this order (dims_null: the message
+// for a NULL size array; words / bytes_fn: the plan's size rule and the query that gives it; op: an operator's place in it).
+static int ragged_plan_buffer(bool have_dims, const char* dims_null, const void* host_buf, int B, size_t bytes, size_t (*words)(int),
+                              const char* bytes_fn, RaggedOp* op = nullptr, int num_coeffs_or_0 = 0) {
+  if (!have_dims) return fail(CURL_E_NULL, dims_null);
+  if (!host_buf) return fail(CURL_E_NULL, "host_buf is NULL");
+  if (B < 1) return fail(CURL_E_SHAPE, "ragged batch: B must be positive");
+  if (B > kRaggedMaxImages) return fail(CURL_E_SHAPE, "B exceeds 65535 images per call");
+  if (op)
+    if (int rc = ragged_op(num_coeffs_or_0, *op)) return rc;
+  if ((uintptr_t)host_buf % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer must be 8-byte aligned");
+  if (bytes < words(B) * sizeof(int)) return ragged_failf(CURL_E_WORKSPACE, "ragged batch: the plan buffer is too small (%s)", bytes_fn);
+  return 0;
+}
+// ... and of every image's size
+static int ragged_image_size(int H, int W) {
+  if (H <= 0 || W <= 0) return fail(CURL_E_SHAPE, "ragged batch: every H and W must be positive");
+  if ((uint64_t)H * (uint64_t)W > (1ull << 30)) return fail(CURL_E_SHAPE, "ragged batch: an image's H*W exceeds 2^30 pixels");
+  return 0;
+}
+
 static int ragged_build(int B, const int* H, const int* W, const int* C, bool has_mask, const RaggedOp& op, int* p) {
   int n_dword = 0;
   uint64_t hash = 1469598103934665603ull;
   hash = ragged_hash_word(ragged_hash_word(ragged_hash_word(hash, (uint32_t)op.count), has_mask), (uint32_t)B);
   for (int i = 0; i < B; ++i) {
-    if (H[i] <= 0 || W[i] <= 0) return fail(CURL_E_SHAPE, "ragged batch: every H and W must be positive");
-    if ((uint64_t)H[i] * (uint64_t)W[i] > (1ull << 30)) return fail(CURL_E_SHAPE, "ragged batch: an image's H*W exceeds 2^30 pixels");
+    if (int rc = ragged_image_size(H[i], W[i])) return rc;
     if (C[i] != 3 && C[i] != 4) return fail(CURL_E_SHAPE, "ragged batch: channels must be 3 (RGB) or 4 (RGBA)");
     n_dword += ragged_is_dword(op, H[i], W[i]);
     hash = ragged_hash_word(ragged_hash_word(ragged_hash_word(hash, (uint32_t)H[i]), (uint32_t)W[i]), (uint32_t)C[i]);
@@ -122,18 +144,22 @@ static int ragged_host_plan(const void* host_plan) {
   return 0;
 }
 
-// every check of a launch entry that the two share, in the header's order; no HIP call
-static int check_ragged(RaggedArgs& r, const uint8_t* img, size_t img_bytes, const uint8_t* mask, size_t mask_bytes, uint8_t* out,
-                        size_t out_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes, int op_count, unsigned flags) {
-  if (!img || !out) return fail(CURL_E_NULL, "arena pointer is NULL");
+// what a launch entry asks of the plan, in the header's order (its host copy, flags, operator, masks, device copy); no HIP call
+static int check_ragged_plan(const void* host_plan, const void* plan_dev, size_t plan_bytes, int op_count, unsigned flags, bool masks) {
   if (!plan_dev) return fail(CURL_E_NULL, "plan_dev is NULL");
   if (int rc = ragged_host_plan(host_plan)) return rc;
   if (flags) return fail(CURL_E_FLAGS, "unsupported flag bit for this entry point (flags must be 0)");
   const int* p = static_cast<const int*>(host_plan);
   if (p[RH_OP] != op_count) return fail(CURL_E_WORKSPACE, "ragged batch: the plan was made for another operator");
-  if (mask && !p[RH_HAS_MASK]) return fail(CURL_E_WORKSPACE, "ragged batch: a mask arena with a plan that was made without masks");
+  if (masks && !p[RH_HAS_MASK]) return fail(CURL_E_WORKSPACE, "ragged batch: a mask arena with a plan that was made without masks");
   if ((uintptr_t)plan_dev % 8) return fail(CURL_E_WORKSPACE, "ragged batch: plan_dev must be 8-byte aligned");
   if (plan_bytes < ragged_plan_words(p[RH_B]) * sizeof(int)) return fail(CURL_E_WORKSPACE, "ragged batch: plan_dev is too small (curl_ragged_plan_bytes)");
+  return 0;
+}
+// ... and of the three arenas of a forward entry, behind it: each as large as the (checked) plan's, on the dword grid -> r
+static int check_ragged_arenas(RaggedArgs& r, const uint8_t* img, size_t img_bytes, const uint8_t* mask, size_t mask_bytes, uint8_t* out,
+                               size_t out_bytes, const void* host_plan, const void* plan_dev) {
+  const int* p = static_cast<const int*>(host_plan);
   if (img_bytes < get64(p + RH_IMG_BYTES)) return fail(CURL_E_WORKSPACE, "ragged batch: the image arena is smaller than the plan's");
   if (mask && mask_bytes < get64(p + RH_MASK_BYTES)) return fail(CURL_E_WORKSPACE, "ragged batch: the mask arena is smaller than the plan's");
   if (out_bytes < get64(p + RH_OUT_BYTES)) return fail(CURL_E_WORKSPACE, "ragged batch: the out arena is smaller than the plan's");
@@ -144,11 +170,22 @@ static int check_ragged(RaggedArgs& r, const uint8_t* img, size_t img_bytes, con
   r.hash = get64(p + RH_HASH), r.stamp = kRaggedStamp;
   return 0;
 }
+// every check that the forward entries share; fg: the foreground entries', which need the masks
+static int check_ragged(RaggedArgs& r, const uint8_t* img, size_t img_bytes, const uint8_t* mask, size_t mask_bytes, uint8_t* out,
+                        size_t out_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes, int op_count, unsigned flags,
+                        bool fg = false) {
+  if (!img || !out) return fail(CURL_E_NULL, "arena pointer is NULL");
+  if (fg && !mask) return fail(CURL_E_MASK, "mask_arena is NULL (the foreground entries need the masks)");
+  if (int rc = check_ragged_plan(host_plan, plan_dev, plan_bytes, op_count, flags, mask != nullptr)) return rc;
+  return check_ragged_arenas(r, img, img_bytes, mask, mask_bytes, out, out_bytes, host_plan, plan_dev);
+}
 
+// the two kernels of a forward entry (stream_ragged_kernel's or stream_ragged_fg_kernel's): the dword and the byte class's
+typedef void (*StreamRaggedKernel)(StreamArgs, const int*, const uint8_t*, const uint8_t*, uint8_t*, unsigned long long, unsigned long long,
+                                   unsigned long long, unsigned long long, unsigned, unsigned, unsigned);
 // one launch per non-empty class (the curve collapse first); everything is checked by now
-template <class Op>
-static int launch_stream_ragged(RaggedArgs r, const void* host_plan, const float* coef, unsigned coef_stride, hipStream_t s,
-                                const char* name, const PrepArgs* prep = nullptr) {
+static int launch_stream_ragged(StreamRaggedKernel dword, StreamRaggedKernel byte, RaggedArgs r, const void* host_plan, const float* coef,
+                                unsigned coef_stride, hipStream_t s, const char* name, const PrepArgs* prep = nullptr) {
   const int* p = static_cast<const int*>(host_plan);
   if (prep)
     if (int rc = launch_prep(*prep, p[RH_B], s)) return rc;
@@ -157,15 +194,60 @@ static int launch_stream_ragged(RaggedArgs r, const void* host_plan, const float
   a.coef_stride = coef_stride;
   if (p[RH_N_DWORD] > 0) {
     r.table = kRaggedHeaderWords, r.count = (unsigned)p[RH_N_DWORD];
-    hipLaunchKernelGGL((stream_ragged_kernel<Op, 4, true>), dim3((unsigned)p[RH_GRID_DWORD]), dim3((unsigned)p[RH_THREADS_DWORD]), 0, s, a, r.plan, r.img, r.mask, r.out,
-                       r.img_bytes, r.mask_bytes, r.out_bytes, r.hash, r.stamp, r.table, r.count);
+    hipLaunchKernelGGL(dword, dim3((unsigned)p[RH_GRID_DWORD]), dim3((unsigned)p[RH_THREADS_DWORD]), 0, s, a, r.plan, r.img, r.mask, r.out, r.img_bytes,
+                       r.mask_bytes, r.out_bytes, r.hash, r.stamp, r.table, r.count);
   }
   if (p[RH_N_BYTE] > 0) {
     r.table = kRaggedHeaderWords + (unsigned)p[RH_N_DWORD] * kRaggedDescWords, r.count = (unsigned)p[RH_N_BYTE];
-    hipLaunchKernelGGL((stream_ragged_kernel<Op, 1, false>), dim3((unsigned)p[RH_GRID_BYTE]), dim3((unsigned)p[RH_THREADS_BYTE]), 0, s, a, r.plan, r.img, r.mask, r.out,
-                       r.img_bytes, r.mask_bytes, r.out_bytes, r.hash, r.stamp, r.table, r.count);
+    hipLaunchKernelGGL(byte, dim3((unsigned)p[RH_GRID_BYTE]), dim3((unsigned)p[RH_THREADS_BYTE]), 0, s, a, r.plan, r.img, r.mask, r.out, r.img_bytes,
+                       r.mask_bytes, r.out_bytes, r.hash, r.stamp, r.table, r.count);
   }
   return hip_done(name);
+}
+
+// the two forward entries and, with fg, their foreground twins (host_api_ragged_fg.inc): the masks required, the _fg_ kernels
+static int trispace_fwd_ragged(const uint8_t* img_arena, size_t img_bytes, const float* coeffs, const uint8_t* mask_arena, size_t mask_bytes,
+                               uint8_t* out_arena, size_t out_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes,
+                               int num_coeffs, unsigned flags, curl_stream_t stream, bool fg) {
+  g_err[0] = 0;
+  if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
+  if (!img_arena || !out_arena) return fail(CURL_E_NULL, "arena pointer is NULL");
+  int order;
+  if (int rc = unpack_num_coeffs(num_coeffs, num_coeffs, order)) return rc;
+  RaggedArgs r{};
+  if (int rc = check_ragged(r, img_arena, img_bytes, mask_arena, mask_bytes, out_arena, out_bytes, host_plan, plan_dev, plan_bytes,
+                            num_coeffs, flags, fg))
+    return rc;
+  if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  return dispatch_order(num_coeffs, [&](auto V, auto D) {
+    typedef TriSpaceOp<V, D> T;
+    typedef typename T::Op Op;
+    if (fg)
+      return launch_stream_ragged(stream_ragged_fg_kernel<Op, 4, true>, stream_ragged_fg_kernel<Op, 1, false>, r, host_plan, coeffs,
+                                  T::kCoefStride, s, T::kRows ? "trispace_rows_ragged_fg_u8hwc" : "trispace_ragged_fg_u8hwc");
+    return launch_stream_ragged(stream_ragged_kernel<Op, 4, true>, stream_ragged_kernel<Op, 1, false>, r, host_plan, coeffs, T::kCoefStride,
+                                s, T::kRows ? "trispace_rows_ragged_u8hwc" : "trispace_ragged_u8hwc");
+  });
+}
+
+static int layer_fwd_ragged(const uint8_t* img_arena, size_t img_bytes, const float* rawL, const float* rawR, const float* rawH,
+                            const uint8_t* mask_arena, size_t mask_bytes, uint8_t* out_arena, size_t out_bytes, float* reg, void* workspace,
+                            size_t workspace_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes, int Kl, int Kr, int Kh,
+                            unsigned flags, curl_stream_t stream, bool fg) {
+  g_err[0] = 0;
+  RaggedArgs r{};
+  if (int rc = check_ragged(r, img_arena, img_bytes, mask_arena, mask_bytes, out_arena, out_bytes, host_plan, plan_dev, plan_bytes, 0,
+                            flags, fg))
+    return rc;
+  KnotSetup k;
+  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, true, workspace, workspace_bytes, static_cast<const int*>(host_plan)[RH_B], reg))
+    return rc;
+  if (fg)
+    return launch_stream_ragged(stream_ragged_fg_kernel<OpLayer, 4, true>, stream_ragged_fg_kernel<OpLayer, 1, false>, r, host_plan, k.ws,
+                                k.stride, (hipStream_t)stream, "curl_layer_ragged_fg_u8hwc", &k.prep);
+  return launch_stream_ragged(stream_ragged_kernel<OpLayer, 4, true>, stream_ragged_kernel<OpLayer, 1, false>, r, host_plan, k.ws, k.stride,
+                              (hipStream_t)stream, "curl_layer_ragged_u8hwc", &k.prep);
 }
 
 extern "C" {
@@ -179,14 +261,10 @@ size_t curl_ragged_plan_bytes(int B, int num_coeffs_or_0) {
 int curl_ragged_plan(int B, const int* H, const int* W, const int* channels, int has_mask, int num_coeffs_or_0, void* host_buf,
                      size_t bytes) {
   g_err[0] = 0;
-  if (!H || !W || !channels) return fail(CURL_E_NULL, "H / W / channels is NULL");
-  if (!host_buf) return fail(CURL_E_NULL, "host_buf is NULL");
-  if (B < 1) return fail(CURL_E_SHAPE, "ragged batch: B must be positive");
-  if (B > kRaggedMaxImages) return fail(CURL_E_SHAPE, "B exceeds 65535 images per call");
   RaggedOp op;
-  if (int rc = ragged_op(num_coeffs_or_0, op)) return rc;
-  if ((uintptr_t)host_buf % 8) return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer must be 8-byte aligned");
-  if (bytes < ragged_plan_words(B) * sizeof(int)) return fail(CURL_E_WORKSPACE, "ragged batch: the plan buffer is too small (curl_ragged_plan_bytes)");
+  if (int rc = ragged_plan_buffer(H && W && channels, "H / W / channels is NULL", host_buf, B, bytes, ragged_plan_words,
+                                  "curl_ragged_plan_bytes", &op, num_coeffs_or_0))
+    return rc;
   return ragged_build(B, H, W, channels, has_mask != 0, op, static_cast<int*>(host_buf));
 }
 
@@ -202,22 +280,8 @@ int curl_ragged_arena_bytes(const void* host_plan, size_t* img_bytes, size_t* ma
 int curl_trispace_fwd_ragged_u8hwc(const uint8_t* img_arena, size_t img_bytes, const float* coeffs, const uint8_t* mask_arena,
                                    size_t mask_bytes, uint8_t* out_arena, size_t out_bytes, const void* host_plan,
                                    const void* plan_dev, size_t plan_bytes, int num_coeffs, unsigned flags, curl_stream_t stream) {
-  g_err[0] = 0;
-  if (!coeffs) return fail(CURL_E_NULL, "coeffs is NULL");
-  if (!img_arena || !out_arena) return fail(CURL_E_NULL, "arena pointer is NULL");
-  int order;
-  if (int rc = unpack_num_coeffs(num_coeffs, num_coeffs, order)) return rc;
-  RaggedArgs r{};
-  if (int rc = check_ragged(r, img_arena, img_bytes, mask_arena, mask_bytes, out_arena, out_bytes, host_plan, plan_dev, plan_bytes,
-                            num_coeffs, flags))
-    return rc;
-  if (int rc = check_coeffs_aligned(coeffs, num_coeffs)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  return dispatch_order(num_coeffs, [&](auto V, auto D) {
-    typedef TriSpaceOp<V, D> T;
-    return launch_stream_ragged<typename T::Op>(r, host_plan, coeffs, T::kCoefStride, s,
-                                                T::kRows ? "trispace_rows_ragged_u8hwc" : "trispace_ragged_u8hwc");
-  });
+  return trispace_fwd_ragged(img_arena, img_bytes, coeffs, mask_arena, mask_bytes, out_arena, out_bytes, host_plan, plan_dev, plan_bytes,
+                             num_coeffs, flags, stream, false);
 }
 
 int curl_layer_fwd_ragged_u8hwc(const uint8_t* img_arena, size_t img_bytes, const float* rawL, const float* rawR,
@@ -225,15 +289,9 @@ int curl_layer_fwd_ragged_u8hwc(const uint8_t* img_arena, size_t img_bytes, cons
                                 size_t out_bytes, float* reg, void* workspace, size_t workspace_bytes, const void* host_plan,
                                 const void* plan_dev, size_t plan_bytes, int Kl, int Kr, int Kh, unsigned flags,
                                 curl_stream_t stream) {
-  g_err[0] = 0;
-  RaggedArgs r{};
-  if (int rc = check_ragged(r, img_arena, img_bytes, mask_arena, mask_bytes, out_arena, out_bytes, host_plan, plan_dev, plan_bytes, 0,
-                            flags))
-    return rc;
-  KnotSetup k;
-  if (int rc = layer_knots(k, rawL, rawR, rawH, Kl, Kr, Kh, true, workspace, workspace_bytes, static_cast<const int*>(host_plan)[RH_B], reg))
-    return rc;
-  return launch_stream_ragged<OpLayer>(r, host_plan, k.ws, k.stride, (hipStream_t)stream, "curl_layer_ragged_u8hwc", &k.prep);
+  return layer_fwd_ragged(img_arena, img_bytes, rawL, rawR, rawH, mask_arena, mask_bytes, out_arena, out_bytes, reg, workspace,
+                          workspace_bytes, host_plan, plan_dev, plan_bytes, Kl, Kr, Kh, flags, stream, false);
 }
 
 }  // extern "C"
+

@@ -18,17 +18,14 @@ int curl_sse_ragged_u8hwc(const uint8_t* a_arena, size_t a_bytes, const uint8_t*
                           size_t workspace_bytes, const void* host_plan, const void* plan_dev, size_t plan_bytes, unsigned flags,
                           curl_stream_t stream) {
   g_err[0] = 0;
-  // check_ragged's checks in its order: its image and out arenas are a and b here, both held to the plan's OUT arena (an image
-  // arena of RGBA images is larger), so its size checks of the two are made below with the arenas' own names
-  RaggedArgs r{};
+  // the forward entries' order: the plan, then the arenas -- a and b both held to the plan's OUT arena (an image arena of RGBA
+  // images is larger), under their own names
   if (!a_arena || !b_arena) return fail(CURL_E_NULL, "arena pointer is NULL");
-  if (!plan_dev) return fail(CURL_E_NULL, "plan_dev is NULL");
-  if (int rc = ragged_host_plan(host_plan)) return rc;
+  if (int rc = check_ragged_plan(host_plan, plan_dev, plan_bytes, 0, flags, mask_arena != nullptr)) return rc;
   const int* p = static_cast<const int*>(host_plan);
   const uint64_t rgb_bytes = get64(p + RH_OUT_BYTES);
-  if (int rc = check_ragged(r, a_arena, (size_t)get64(p + RH_IMG_BYTES), mask_arena, mask_bytes, const_cast<uint8_t*>(b_arena),
-                            (size_t)rgb_bytes, host_plan, plan_dev, plan_bytes, 0, flags))
-    return rc;
+  if (mask_arena && mask_bytes < get64(p + RH_MASK_BYTES)) return fail(CURL_E_WORKSPACE, "ragged batch: the mask arena is smaller than the plan's");
+  if (!on_grid(4, a_arena, mask_arena, b_arena)) return fail(CURL_E_SHAPE, "ragged batch: the arenas must be 4-byte aligned");
   if (a_bytes < rgb_bytes) return fail(CURL_E_WORKSPACE, "ragged score: the a arena is smaller than the plan's out arena");
   if (b_bytes < rgb_bytes) return fail(CURL_E_WORKSPACE, "ragged score: the b arena is smaller than the plan's out arena");
   const unsigned B = (unsigned)p[RH_B];
@@ -42,17 +39,19 @@ int curl_sse_ragged_u8hwc(const uint8_t* a_arena, size_t a_bytes, const uint8_t*
 
   hipStream_t s = (hipStream_t)stream;
   ScorePartial* partial = static_cast<ScorePartial*>(workspace);
+  const int* plan = static_cast<const int*>(plan_dev);
+  const unsigned long long hash = get64(p + RH_HASH);
   const unsigned n_dword = (unsigned)p[RH_N_DWORD], grid_dword = (unsigned)p[RH_GRID_DWORD], grid_byte = (unsigned)p[RH_GRID_BYTE];
   const unsigned long long mb = mask_arena ? mask_bytes : 0;
   if (n_dword > 0)
-    hipLaunchKernelGGL((sse_ragged_partial_kernel<4>), dim3(grid_dword), dim3(256), 0, s, r.plan, a_arena, b_arena, mask_arena, partial,
-                       (unsigned long long)a_bytes, (unsigned long long)b_bytes, mb, r.hash, r.stamp, kRaggedHeaderWords, n_dword);
+    hipLaunchKernelGGL((sse_ragged_partial_kernel<4>), dim3(grid_dword), dim3(256), 0, s, plan, a_arena, b_arena, mask_arena, partial,
+                       (unsigned long long)a_bytes, (unsigned long long)b_bytes, mb, hash, kRaggedStamp, kRaggedHeaderWords, n_dword);
   if (p[RH_N_BYTE] > 0)
-    hipLaunchKernelGGL((sse_ragged_partial_kernel<1>), dim3(grid_byte), dim3(256), 0, s, r.plan, a_arena, b_arena, mask_arena,
-                       partial + 2 * (size_t)grid_dword, (unsigned long long)a_bytes, (unsigned long long)b_bytes, mb, r.hash, r.stamp,
+    hipLaunchKernelGGL((sse_ragged_partial_kernel<1>), dim3(grid_byte), dim3(256), 0, s, plan, a_arena, b_arena, mask_arena,
+                       partial + 2 * (size_t)grid_dword, (unsigned long long)a_bytes, (unsigned long long)b_bytes, mb, hash, kRaggedStamp,
                        kRaggedHeaderWords + n_dword * kRaggedDescWords, (unsigned)p[RH_N_BYTE]);
-  hipLaunchKernelGGL(sse_ragged_final_kernel, dim3(B), dim3(256), 0, s, r.plan, partial, reinterpret_cast<unsigned long long*>(sums), r.hash,
-                     r.stamp, B, n_dword, grid_dword, grid_byte);
+  hipLaunchKernelGGL(sse_ragged_final_kernel, dim3(B), dim3(256), 0, s, plan, partial, reinterpret_cast<unsigned long long*>(sums), hash,
+                     kRaggedStamp, B, n_dword, grid_dword, grid_byte);
   return hip_done("curl_sse_ragged_u8hwc");
 }
 

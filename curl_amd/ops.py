@@ -1060,26 +1060,43 @@ class _RaggedPlan:
         self.img_off, self.mask_off, self.out_off = ([int(v) for v in off[order, k]] for k in range(3))
 
 
+def _cached_plan(cache, kept, key, build):
+    """cache[key]; a plan that is not there yet is built (build(): on the host by the library, then uploaded) and kept, the
+    oldest of `kept` plans dropped for it."""
+    plan = cache.get(key)
+    if plan is None:
+        plan = build()
+        if len(cache) >= kept:
+            del cache[next(iter(cache))]
+        cache[key] = plan
+    return plan
+
+
+def _host_plan(builder, shapes, channels, max_images, tail, size_args=lambda hs, ws: ()):
+    """The host copy (int32) of the plan the library's `builder` makes of a shape list: builder(B, H, W[, channels], *tail,
+    buffer, bytes), the buffer sized by builder + "_bytes" (B, *size_args(H, W))."""
+    import numpy as np
+    lib = _lib.load()
+    B = len(shapes)
+    if B > max_images:
+        raise ValueError(f"a ragged batch holds at most {max_images} images, got {B}")
+    dims = [[s[0] for s in shapes], [s[1] for s in shapes]] + ([channels] if channels is not None else [])
+    dims = [np.ascontiguousarray(v, dtype=np.int32) for v in dims]
+    ptrs = [d.ctypes.data for d in dims]
+    nbytes = getattr(lib, builder + "_bytes")(B, *size_args(*ptrs[:2]))
+    host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
+    _lib.check(getattr(lib, builder)(B, *ptrs, *tail, host.data_ptr(), nbytes), builder)
+    return host
+
+
 def _ragged_plan(shapes, channels, has_mask, nc_arg, device):
     """The plan of a shape list for one operator (nc_arg: the entries' num_coeffs, 0 = the curve layer), built on the host by
     the library, uploaded once and kept (device None: host only); the oldest of more than sixteen is dropped."""
-    key = (tuple(shapes), tuple(channels), bool(has_mask), nc_arg, device)
-    plan = _ragged_plans.get(key)
-    if plan is None:
-        import numpy as np
-        lib = _lib.load()
-        B = len(shapes)
-        if B > _lib.RAGGED_MAX_IMAGES:
-            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
-        nbytes = lib.curl_ragged_plan_bytes(B, nc_arg)
-        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
-        hs, ws, cs = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes], channels))
-        _lib.check(lib.curl_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, cs.ctypes.data, int(bool(has_mask)), nc_arg,
-                                        host.data_ptr(), nbytes), "curl_ragged_plan")
-        if len(_ragged_plans) >= _RAGGED_PLANS_KEPT:
-            del _ragged_plans[next(iter(_ragged_plans))]
-        plan = _ragged_plans[key] = _RaggedPlan(host, host.to(device) if device is not None else None)
-    return plan
+    def build():
+        host = _host_plan("curl_ragged_plan", shapes, channels, _lib.RAGGED_MAX_IMAGES, (int(bool(has_mask)), nc_arg),
+                          lambda hs, ws: (nc_arg,))
+        return _RaggedPlan(host, host.to(device) if device is not None else None)
+    return _cached_plan(_ragged_plans, _RAGGED_PLANS_KEPT, (tuple(shapes), tuple(channels), bool(has_mask), nc_arg, device), build)
 
 
 class RaggedBytes:
@@ -1188,52 +1205,14 @@ def _ragged_empty(images, device):
     return len(images) == 0, device
 
 
-def trispace_forward_u8hwc_ragged(images, coeffs, white_masks=None):
-    """trispace_forward_u8hwc for a batch of images of different sizes in one launch per class of images (dword / byte):
-    images a RaggedBytes or a list of uint8 [H,W,3|4] (alpha is not read), coeffs [B,3,3,n], white_masks None or one [H,W]
-    uint8 mask per image (a RaggedBytes or a list).  -> RaggedBytes of the [H,W,3] outputs; every image's bytes equal
-    trispace_forward_u8hwc of that image alone."""
-    empty, device = _ragged_empty(images, coeffs.device if isinstance(coeffs, torch.Tensor) else None)
-    if empty:
-        return RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], [])
-    lib = _lib.load()
-    rb, wm = _ragged_inputs(images, white_masks, device)
-    _check_coeffs(coeffs, len(rb))
-    _check_same_device([("images", rb.arena), ("coeffs", coeffs)])
-    c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
-    nc = _nc_arg(c.shape[3])
-    plan, out = _ragged_arenas(rb, wm, nc)
-    with torch.cuda.device(rb.device):
-        rc = lib.curl_trispace_fwd_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), c.data_ptr(), _ptr(wm.arena if wm is not None else None),
-                                                wm.arena.numel() if wm else 0, out.arena.data_ptr(), out.arena.numel(),
-                                                plan.host.data_ptr(), plan.dev.data_ptr(), plan.nbytes, nc, 0, _stream(rb.arena))
-    _lib.check(rc, "curl_trispace_fwd_ragged_u8hwc")
-    return out
+def _mask_args(wm):
+    """The mask arena's two arguments of a ragged entry: (pointer, bytes), (0, 0) without masks."""
+    return (0, 0) if wm is None else (wm.arena.data_ptr(), wm.arena.numel())
 
 
-def curl_layer_forward_u8hwc_ragged(images, L, R, H, white_masks=None):
-    """curl_layer_forward_u8hwc(img, None, L, R, H, white_mask) for a batch of images of different sizes: one curve collapse
-    for the B knot rows and one launch per class of images.  -> (RaggedBytes of the [H,W,3] outputs, reg [B]); bytes and reg
-    equal the single-image calls'."""
-    empty, device = _ragged_empty(images, L.device if isinstance(L, torch.Tensor) else None)
-    if empty:
-        return (RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], []),
-                torch.zeros(0, dtype=torch.float32, device=device))
-    lib = _lib.load()
-    rb, wm = _ragged_inputs(images, white_masks, device)
-    B = len(rb)
-    Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
-    _check_same_device([("images", rb.arena), ("L", Lc), ("R", Rc), ("H", Hc)])
-    plan, out = _ragged_arenas(rb, wm, 0)
-    reg = torch.empty(B, dtype=torch.float32, device=rb.device)
-    ws, nbytes = _workspace(B, n_knots, rb.device)
-    with torch.cuda.device(rb.device):
-        rc = lib.curl_layer_fwd_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
-                                             _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm else 0, out.arena.data_ptr(),
-                                             out.arena.numel(), reg.data_ptr(), ws.data_ptr(), nbytes, plan.host.data_ptr(),
-                                             plan.dev.data_ptr(), plan.nbytes, Kl, Kr, Kh, 0, _stream(rb.arena))
-    _lib.check(rc, "curl_layer_fwd_ragged_u8hwc")
-    return out, reg
+def _ragged_sizes(x):
+    """The shapes of the images or masks of a ragged call, as given: a RaggedBytes' or a list's."""
+    return [tuple(s) for s in x.shapes] if isinstance(x, RaggedBytes) else [tuple(t.shape) for t in x]
 
 
 def _ragged_fg_masks(images, fg_masks):
@@ -1241,10 +1220,7 @@ def _ragged_fg_masks(images, fg_masks):
     mask of each image's size (_ragged_inputs holds the packed arenas to the same)."""
     if fg_masks is None:
         raise ValueError("fg_masks is required (one uint8 [H,W] 'L' mask per image)")
-
-    def sizes(x):
-        return [tuple(s) for s in x.shapes] if isinstance(x, RaggedBytes) else [tuple(t.shape) for t in x]
-    want, got = [s[:2] for s in sizes(images)], sizes(fg_masks)
+    want, got = [s[:2] for s in _ragged_sizes(images)], _ragged_sizes(fg_masks)
     if len(got) != len(want):
         raise ValueError(f"fg_masks must hold one mask per image ({len(want)}), got {len(got)}")
     if got != want:
@@ -1253,53 +1229,80 @@ def _ragged_fg_masks(images, fg_masks):
         raise ValueError(f"fg_masks must be uint8 [H,W] masks, got {[str(t.dtype) for t in fg_masks]}")
 
 
-def trispace_foreground_u8hwc_ragged(images, coeffs, fg_masks):
-    """trispace_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result:
-    wavefronts whose mask bytes are all 0 store white and never read their pixels, workgroups of such wavefronts stage no
-    table (curl_trispace_fwd_ragged_fg_u8hwc).  The same inputs, fg_masks required; the cached plan of a shape list is the
-    plain call's.  -> RaggedBytes of the [H,W,3] outputs."""
+def _trispace_u8hwc_ragged(images, coeffs, masks, fg):
+    """The two ragged polynomial ops: the plain entry, or with fg the foreground one (its masks required, and checked first)."""
     empty, device = _ragged_empty(images, coeffs.device if isinstance(coeffs, torch.Tensor) else None)
-    _ragged_fg_masks(images, fg_masks)
+    if fg:
+        _ragged_fg_masks(images, masks)
     if empty:
         return RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], [])
     lib = _lib.load()
-    rb, wm = _ragged_inputs(images, fg_masks, device)
+    rb, wm = _ragged_inputs(images, masks, device)
     _check_coeffs(coeffs, len(rb))
     _check_same_device([("images", rb.arena), ("coeffs", coeffs)])
     c = _coeffs32(coeffs, pairs=coeffs.shape[3] == 126)
     nc = _nc_arg(c.shape[3])
     plan, out = _ragged_arenas(rb, wm, nc)
+    entry = "curl_trispace_fwd_ragged_fg_u8hwc" if fg else "curl_trispace_fwd_ragged_u8hwc"
     with torch.cuda.device(rb.device):
-        rc = lib.curl_trispace_fwd_ragged_fg_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), c.data_ptr(), wm.arena.data_ptr(), wm.arena.numel(),
-                                                   out.arena.data_ptr(), out.arena.numel(), plan.host.data_ptr(), plan.dev.data_ptr(),
-                                                   plan.nbytes, nc, 0, _stream(rb.arena))
-    _lib.check(rc, "curl_trispace_fwd_ragged_fg_u8hwc")
+        rc = getattr(lib, entry)(rb.arena.data_ptr(), rb.arena.numel(), c.data_ptr(), *_mask_args(wm), out.arena.data_ptr(),
+                                 out.arena.numel(), plan.host.data_ptr(), plan.dev.data_ptr(), plan.nbytes, nc, 0, _stream(rb.arena))
+    _lib.check(rc, entry)
     return out
 
 
-def curl_layer_foreground_u8hwc_ragged(images, L, R, H, fg_masks):
-    """curl_layer_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result and
-    the same reg (curl_layer_fwd_ragged_fg_u8hwc).  -> (RaggedBytes of the [H,W,3] outputs, reg [B])."""
+def _curl_layer_u8hwc_ragged(images, L, R, H, masks, fg):
+    """The two ragged curve-layer ops: the plain entry, or with fg the foreground one (its masks required, and checked first)."""
     empty, device = _ragged_empty(images, L.device if isinstance(L, torch.Tensor) else None)
-    _ragged_fg_masks(images, fg_masks)
+    if fg:
+        _ragged_fg_masks(images, masks)
     if empty:
         return (RaggedBytes(torch.empty(0, dtype=torch.uint8, device=device), [], [], []),
                 torch.zeros(0, dtype=torch.float32, device=device))
     lib = _lib.load()
-    rb, wm = _ragged_inputs(images, fg_masks, device)
+    rb, wm = _ragged_inputs(images, masks, device)
     B = len(rb)
     Lc, Rc, Hc, Kl, Kr, Kh, n_knots = _layer_knots(L, R, H, B)
     _check_same_device([("images", rb.arena), ("L", Lc), ("R", Rc), ("H", Hc)])
     plan, out = _ragged_arenas(rb, wm, 0)
     reg = torch.empty(B, dtype=torch.float32, device=rb.device)
     ws, nbytes = _workspace(B, n_knots, rb.device)
+    entry = "curl_layer_fwd_ragged_fg_u8hwc" if fg else "curl_layer_fwd_ragged_u8hwc"
     with torch.cuda.device(rb.device):
-        rc = lib.curl_layer_fwd_ragged_fg_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(),
-                                                wm.arena.data_ptr(), wm.arena.numel(), out.arena.data_ptr(), out.arena.numel(),
-                                                reg.data_ptr(), ws.data_ptr(), nbytes, plan.host.data_ptr(), plan.dev.data_ptr(),
-                                                plan.nbytes, Kl, Kr, Kh, 0, _stream(rb.arena))
-    _lib.check(rc, "curl_layer_fwd_ragged_fg_u8hwc")
+        rc = getattr(lib, entry)(rb.arena.data_ptr(), rb.arena.numel(), Lc.data_ptr(), Rc.data_ptr(), Hc.data_ptr(), *_mask_args(wm),
+                                 out.arena.data_ptr(), out.arena.numel(), reg.data_ptr(), ws.data_ptr(), nbytes, plan.host.data_ptr(),
+                                 plan.dev.data_ptr(), plan.nbytes, Kl, Kr, Kh, 0, _stream(rb.arena))
+    _lib.check(rc, entry)
     return out, reg
+
+
+def trispace_forward_u8hwc_ragged(images, coeffs, white_masks=None):
+    """trispace_forward_u8hwc for a batch of images of different sizes in one launch per class of images (dword / byte):
+    images a RaggedBytes or a list of uint8 [H,W,3|4] (alpha is not read), coeffs [B,3,3,n], white_masks None or one [H,W]
+    uint8 mask per image (a RaggedBytes or a list).  -> RaggedBytes of the [H,W,3] outputs; every image's bytes equal
+    trispace_forward_u8hwc of that image alone."""
+    return _trispace_u8hwc_ragged(images, coeffs, white_masks, False)
+
+
+def curl_layer_forward_u8hwc_ragged(images, L, R, H, white_masks=None):
+    """curl_layer_forward_u8hwc(img, None, L, R, H, white_mask) for a batch of images of different sizes: one curve collapse
+    for the B knot rows and one launch per class of images.  -> (RaggedBytes of the [H,W,3] outputs, reg [B]); bytes and reg
+    equal the single-image calls'."""
+    return _curl_layer_u8hwc_ragged(images, L, R, H, white_masks, False)
+
+
+def trispace_foreground_u8hwc_ragged(images, coeffs, fg_masks):
+    """trispace_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result:
+    wavefronts whose mask bytes are all 0 store white and never read their pixels, workgroups of such wavefronts stage no
+    table (curl_trispace_fwd_ragged_fg_u8hwc).  The same inputs, fg_masks required; the cached plan of a shape list is the
+    plain call's.  -> RaggedBytes of the [H,W,3] outputs."""
+    return _trispace_u8hwc_ragged(images, coeffs, fg_masks, True)
+
+
+def curl_layer_foreground_u8hwc_ragged(images, L, R, H, fg_masks):
+    """curl_layer_forward_u8hwc_ragged with white_masks = fg_masks for segmentation masks, byte for byte the same result and
+    the same reg (curl_layer_fwd_ragged_fg_u8hwc).  -> (RaggedBytes of the [H,W,3] outputs, reg [B])."""
+    return _curl_layer_u8hwc_ragged(images, L, R, H, fg_masks, True)
 
 
 # ------------------------------------------------------------------ the score of a ragged batch (include/curl_hip_ragged_score.h)
@@ -1333,36 +1336,59 @@ def _score_masks(masks, shapes):
         raise ValueError(f"masks must be one uint8 [H,W] mask per image, of the images' sizes {shapes}, got {got}")
 
 
+def _score_device(a, b):
+    """Where the empty result of a score call goes: the device of the side that is a RaggedBytes, else None."""
+    return next((x.device for x in (a, b) if isinstance(x, RaggedBytes)), None)
+
+
+def _score_plan(shapes, has_mask, device):
+    """The plan sse_u8hwc_ragged scores by: the op-0 plan of the shape list as RGB images, whose out arena both sides have."""
+    return _ragged_plan(shapes, [3] * len(shapes), has_mask, 0, device)
+
+
+def _score_inputs(a, b, masks, names, get_plan, rgb_off, check=None):
+    """The front end of the ops that score one ragged byte batch against another: both sides (names: what the messages call
+    them) held to uint8 [H,W,3] images of one shape list and the masks to it, then check(shapes) -- the op's own conditions --
+    all before anything is packed or uploaded; the arenas packed onto one device and held to the offsets (plan.<rgb_off>,
+    plan.mask_off) of get_plan(shapes, has_mask, device).  -> (a's arena, b's, the masks' or None, the plan); four None for
+    an empty batch."""
+    shapes = _score_shapes(a, names[0])
+    if _score_shapes(b, names[1]) != shapes:
+        raise ValueError(f"{names[0]} and {names[1]} must hold images of the same sizes, got {shapes} and {_score_shapes(b, names[1])}")
+    _score_masks(masks, shapes)
+    if check is not None:
+        check(shapes)
+    if not shapes:
+        return None, None, None, None
+    _lib.load()
+    ra, wm = _ragged_inputs(a, masks, None)
+    rb = b if isinstance(b, RaggedBytes) else RaggedBytes.pack(list(b), ra.device)
+    _need_device(rb.arena, names[1])
+    _check_same_device([(names[0], ra.arena), (names[1], rb.arena)])
+    plan = get_plan(ra.shapes, wm is not None, ra.device)
+    off = getattr(plan, rgb_off)
+    if ra.offsets != off or rb.offsets != off or (wm is not None and wm.offsets != plan.mask_off):
+        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
+    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
+        raise ValueError("the arenas must be contiguous")
+    return ra, rb, wm, plan
+
+
 def sse_u8hwc_ragged(a, b, masks=None):
     """The exact masked squared error of two batches of byte images of different sizes, every image in one pass
     (curl_sse_ragged_u8hwc): a and b a RaggedBytes or a list of uint8 [H,W,3] images of the same shape list, masks None or one
     uint8 [H,W] mask per image (a RaggedBytes or a list).  -> int64 [B,2] on the device: [i,0] the sum over the pixels whose
     mask byte is not 0 (all pixels without masks) and the 3 channels of (a - b)^2, [i,1] the number of those pixels.  Integer
     arithmetic throughout: the same bits on every call, for an image alone or in any company and order."""
-    shapes = _score_shapes(a, "a")
-    if _score_shapes(b, "b") != shapes:
-        raise ValueError(f"a and b must hold images of the same sizes, got {shapes} and {_score_shapes(b, 'b')}")
-    _score_masks(masks, shapes)
-    if not shapes:
-        device = next((x.device for x in (a, b) if isinstance(x, RaggedBytes)), None)
-        return torch.zeros((0, 2), dtype=torch.int64, device=device)
+    ra, rb, wm, plan = _score_inputs(a, b, masks, ("a", "b"), _score_plan, "out_off")
+    if plan is None:
+        return torch.zeros((0, 2), dtype=torch.int64, device=_score_device(a, b))
     lib = _lib.load()
-    ra, wm = _ragged_inputs(a, masks, None)
-    rb = b if isinstance(b, RaggedBytes) else RaggedBytes.pack(list(b), ra.device)
-    _need_device(rb.arena, "b")
-    _check_same_device([("a", ra.arena), ("b", rb.arena)])
-    B = len(ra)
-    plan = _ragged_plan(ra.shapes, [3] * B, wm is not None, 0, ra.device)
-    if ra.offsets != plan.out_off or rb.offsets != plan.out_off or (wm is not None and wm.offsets != plan.mask_off):
-        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
-    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
-        raise ValueError("the arenas must be contiguous")
-    sums = torch.empty((B, 2), dtype=torch.int64, device=ra.device)
+    sums = torch.empty((len(ra), 2), dtype=torch.int64, device=ra.device)
     nbytes = lib.curl_ragged_score_workspace_bytes(plan.host.data_ptr())
     ws = torch.empty(nbytes // 8, dtype=torch.int64, device=ra.device)
     with torch.cuda.device(ra.device):
-        rc = lib.curl_sse_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
-                                       _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
+        rc = lib.curl_sse_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(), *_mask_args(wm),
                                        sums.data_ptr(), sums.numel() * 8, ws.data_ptr(), nbytes, plan.host.data_ptr(),
                                        plan.dev.data_ptr(), plan.nbytes, 0, _stream(ra.arena))
     _lib.check(rc, "curl_sse_ragged_u8hwc")
@@ -1400,23 +1426,40 @@ class _MsssimRaggedPlan:
 
 def _msssim_ragged_plan(shapes, has_mask, device):
     """The MS-SSIM plan of a shape list, built on the host by the library, uploaded once and kept, as the op-0 plan is."""
-    key = (tuple(shapes), bool(has_mask), device)
-    plan = _msssim_ragged_plans.get(key)
+    return _pyramid_ragged_plan(_msssim_ragged_plans, "msssim", shapes, has_mask, device)
+
+
+def _pyramid_ragged_plan(cache, kind, shapes, has_mask, device):
+    """The plan of curl_<kind>_ragged_plan (kind: msssim | loss; one layout) of a shape list, kept in `cache`."""
+    def build():
+        host = _host_plan(f"curl_{kind}_ragged_plan", shapes, None, _lib.RAGGED_MAX_IMAGES, (int(bool(has_mask)),))
+        ws_bytes = getattr(_lib.load(), f"curl_{kind}_ragged_workspace_bytes")(host.data_ptr())
+        return _MsssimRaggedPlan(host, host.to(device), ws_bytes)
+    return _cached_plan(cache, _RAGGED_PLANS_KEPT, (tuple(shapes), bool(has_mask), device), build)
+
+
+def _pyramid_stats_u8hwc_ragged(a, b, masks, window_size, rows, kind, get_plan, names, needs):
+    """The body of the two pyramid-statistics ops: curl_<kind>_ragged_u8hwc (kind: msssim | loss) on the plan get_plan gives
+    -> float64 [B,rows,5].  names: what the messages call the two sides; needs: what, in them, needs every side >= 32."""
+    def check(shapes):
+        if window_size not in (1, 3, 5, 7, 9, 11):
+            raise ValueError(f"window_size must be odd and 1..11, got {window_size}")
+        for k, (h, w) in enumerate(shapes):
+            if h < MSSSIM_MIN_SIDE or w < MSSSIM_MIN_SIDE:
+                raise ValueError(f"image {k} is {h}x{w}: {needs} needs H, W >= {MSSSIM_MIN_SIDE} (five pyramid levels, each followed by a 2x2 pooling)")
+    ra, rb, wm, plan = _score_inputs(a, b, masks, names, get_plan, "rgb_off", check)
     if plan is None:
-        import numpy as np
-        lib = _lib.load()
-        B = len(shapes)
-        if B > _lib.RAGGED_MAX_IMAGES:
-            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
-        nbytes = lib.curl_msssim_ragged_plan_bytes(B)
-        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
-        hs, ws = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes]))
-        _lib.check(lib.curl_msssim_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, int(bool(has_mask)), host.data_ptr(), nbytes),
-                   "curl_msssim_ragged_plan")
-        if len(_msssim_ragged_plans) >= _RAGGED_PLANS_KEPT:
-            del _msssim_ragged_plans[next(iter(_msssim_ragged_plans))]
-        plan = _msssim_ragged_plans[key] = _MsssimRaggedPlan(host, host.to(device), lib.curl_msssim_ragged_workspace_bytes(host.data_ptr()))
-    return plan
+        return torch.zeros((0, rows, 5), dtype=torch.float64, device=_score_device(a, b))
+    entry = f"curl_{kind}_ragged_u8hwc"
+    call = getattr(_lib.load(), entry)
+    stats = torch.empty((len(ra), rows, 5), dtype=torch.float64, device=ra.device)
+    ws = torch.empty(plan.ws_bytes // 8, dtype=torch.float64, device=ra.device)
+    with torch.cuda.device(ra.device):
+        rc = call(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(), *_mask_args(wm), stats.data_ptr(),
+                  stats.numel() * 8, ws.data_ptr(), plan.ws_bytes, plan.host.data_ptr(), plan.dev.data_ptr(), plan.nbytes, window_size, 0,
+                  _stream(ra.arena))
+    _lib.check(rc, entry)
+    return stats
 
 
 def msssim_stats_u8hwc_ragged(a, b, masks=None, window_size=11):
@@ -1425,38 +1468,7 @@ def msssim_stats_u8hwc_ragged(a, b, masks=None, window_size=11):
     >= 32), masks None or one uint8 [H,W] mask per image.  -> float64 [B,2,5] on the device: [i,0,l] the mean of level l's SSIM
     map of image i, [i,1,l] that of its contrast-structure map -- msssim_stats of bytes / 255 times (mask != 0), without the
     float images.  The same bits on every call, for an image alone or in any company and order."""
-    shapes = _score_shapes(a, "a")
-    if _score_shapes(b, "b") != shapes:
-        raise ValueError(f"a and b must hold images of the same sizes, got {shapes} and {_score_shapes(b, 'b')}")
-    _score_masks(masks, shapes)
-    if window_size not in (1, 3, 5, 7, 9, 11):
-        raise ValueError(f"window_size must be odd and 1..11, got {window_size}")
-    for k, (h, w) in enumerate(shapes):
-        if h < MSSSIM_MIN_SIDE or w < MSSSIM_MIN_SIDE:
-            raise ValueError(f"image {k} is {h}x{w}: MS-SSIM needs H, W >= {MSSSIM_MIN_SIDE} (five pyramid levels, each followed by a 2x2 pooling)")
-    if not shapes:
-        device = next((x.device for x in (a, b) if isinstance(x, RaggedBytes)), None)
-        return torch.zeros((0, 2, 5), dtype=torch.float64, device=device)
-    lib = _lib.load()
-    ra, wm = _ragged_inputs(a, masks, None)
-    rb = b if isinstance(b, RaggedBytes) else RaggedBytes.pack(list(b), ra.device)
-    _need_device(rb.arena, "b")
-    _check_same_device([("a", ra.arena), ("b", rb.arena)])
-    B = len(ra)
-    plan = _msssim_ragged_plan(ra.shapes, wm is not None, ra.device)
-    if ra.offsets != plan.rgb_off or rb.offsets != plan.rgb_off or (wm is not None and wm.offsets != plan.mask_off):
-        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
-    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
-        raise ValueError("the arenas must be contiguous")
-    stats = torch.empty((B, 2, 5), dtype=torch.float64, device=ra.device)
-    ws = torch.empty(plan.ws_bytes // 8, dtype=torch.float64, device=ra.device)
-    with torch.cuda.device(ra.device):
-        rc = lib.curl_msssim_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
-                                          _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
-                                          stats.data_ptr(), stats.numel() * 8, ws.data_ptr(), plan.ws_bytes, plan.host.data_ptr(),
-                                          plan.dev.data_ptr(), plan.nbytes, window_size, 0, _stream(ra.arena))
-    _lib.check(rc, "curl_msssim_ragged_u8hwc")
-    return stats
+    return _pyramid_stats_u8hwc_ragged(a, b, masks, window_size, 2, "msssim", _msssim_ragged_plan, ("a", "b"), "MS-SSIM")
 
 
 def msssim_from_stats(stats):
@@ -1480,23 +1492,7 @@ _loss_ragged_plans = {}  # (shapes, has_mask, device) -> _MsssimRaggedPlan (the 
 
 def _loss_ragged_plan(shapes, has_mask, device):
     """The loss plan of a shape list, built on the host by the library, uploaded once and kept, as the MS-SSIM plan is."""
-    key = (tuple(shapes), bool(has_mask), device)
-    plan = _loss_ragged_plans.get(key)
-    if plan is None:
-        import numpy as np
-        lib = _lib.load()
-        B = len(shapes)
-        if B > _lib.RAGGED_MAX_IMAGES:
-            raise ValueError(f"a ragged batch holds at most {_lib.RAGGED_MAX_IMAGES} images, got {B}")
-        nbytes = lib.curl_loss_ragged_plan_bytes(B)
-        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
-        hs, ws = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes]))
-        _lib.check(lib.curl_loss_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, int(bool(has_mask)), host.data_ptr(), nbytes),
-                   "curl_loss_ragged_plan")
-        if len(_loss_ragged_plans) >= _RAGGED_PLANS_KEPT:
-            del _loss_ragged_plans[next(iter(_loss_ragged_plans))]
-        plan = _loss_ragged_plans[key] = _MsssimRaggedPlan(host, host.to(device), lib.curl_loss_ragged_workspace_bytes(host.data_ptr()))
-    return plan
+    return _pyramid_ragged_plan(_loss_ragged_plans, "loss", shapes, has_mask, device)
 
 
 def loss_stats_u8hwc_ragged(pred, target, masks=None, window_size=11):
@@ -1507,38 +1503,8 @@ def loss_stats_u8hwc_ragged(pred, target, masks=None, window_size=11):
     then their number N; [i,1,l] / [i,2,l] the means of level l's SSIM and contrast-structure maps of the clamped-L planes.
     The prediction is the BYTES / 255 -- an output file's pixels, not a network's unrounded float output.  The same bits on every
     call, for an image alone or in any company and order."""
-    shapes = _score_shapes(pred, "pred")
-    if _score_shapes(target, "target") != shapes:
-        raise ValueError(f"pred and target must hold images of the same sizes, got {shapes} and {_score_shapes(target, 'target')}")
-    _score_masks(masks, shapes)
-    if window_size not in (1, 3, 5, 7, 9, 11):
-        raise ValueError(f"window_size must be odd and 1..11, got {window_size}")
-    for k, (h, w) in enumerate(shapes):
-        if h < MSSSIM_MIN_SIDE or w < MSSSIM_MIN_SIDE:
-            raise ValueError(f"image {k} is {h}x{w}: the loss's MS-SSIM term needs H, W >= {MSSSIM_MIN_SIDE} (five pyramid levels, each followed by a 2x2 pooling)")
-    if not shapes:
-        device = next((x.device for x in (pred, target) if isinstance(x, RaggedBytes)), None)
-        return torch.zeros((0, 3, 5), dtype=torch.float64, device=device)
-    lib = _lib.load()
-    ra, wm = _ragged_inputs(pred, masks, None)
-    rb = target if isinstance(target, RaggedBytes) else RaggedBytes.pack(list(target), ra.device)
-    _need_device(rb.arena, "target")
-    _check_same_device([("pred", ra.arena), ("target", rb.arena)])
-    B = len(ra)
-    plan = _loss_ragged_plan(ra.shapes, wm is not None, ra.device)
-    if ra.offsets != plan.rgb_off or rb.offsets != plan.rgb_off or (wm is not None and wm.offsets != plan.mask_off):
-        raise ValueError("the arena's offsets are not the plan's (RaggedBytes.pack lays images out as the library does)")
-    if not ra.arena.is_contiguous() or not rb.arena.is_contiguous() or (wm is not None and not wm.arena.is_contiguous()):
-        raise ValueError("the arenas must be contiguous")
-    stats = torch.empty((B, 3, 5), dtype=torch.float64, device=ra.device)
-    ws = torch.empty(plan.ws_bytes // 8, dtype=torch.float64, device=ra.device)
-    with torch.cuda.device(ra.device):
-        rc = lib.curl_loss_ragged_u8hwc(ra.arena.data_ptr(), ra.arena.numel(), rb.arena.data_ptr(), rb.arena.numel(),
-                                        _ptr(wm.arena if wm is not None else None), wm.arena.numel() if wm is not None else 0,
-                                        stats.data_ptr(), stats.numel() * 8, ws.data_ptr(), plan.ws_bytes, plan.host.data_ptr(),
-                                        plan.dev.data_ptr(), plan.nbytes, window_size, 0, _stream(ra.arena))
-    _lib.check(rc, "curl_loss_ragged_u8hwc")
-    return stats
+    return _pyramid_stats_u8hwc_ragged(pred, target, masks, window_size, 3, "loss", _loss_ragged_plan, ("pred", "target"),
+                                       "the loss's MS-SSIM term")
 
 
 def curl_loss_from_stats(stats, shapes):
@@ -1638,23 +1604,11 @@ class _ViewRaggedPlan:
 def _view_ragged_plan(shapes, channels, has_mask, size, device):
     """The plan of a shape list at one size, built on the host by the library, uploaded once and kept; the oldest of more than
     sixteen is dropped."""
-    key = (tuple(shapes), tuple(channels), bool(has_mask), size, device)
-    plan = _view_ragged_plans.get(key)
-    if plan is None:
-        import numpy as np
-        lib = _lib.load()
-        B = len(shapes)
-        if B > _lib.VIEW_RAGGED_MAX_IMAGES:
-            raise ValueError(f"a ragged batch holds at most {_lib.VIEW_RAGGED_MAX_IMAGES} images, got {B}")
-        hs, ws, cs = (np.ascontiguousarray(v, dtype=np.int32) for v in ([s[0] for s in shapes], [s[1] for s in shapes], channels))
-        nbytes = lib.curl_encoder_view_ragged_plan_bytes(B, hs.ctypes.data, ws.ctypes.data, size)
-        host = torch.zeros(max(nbytes, 8) // 4, dtype=torch.int32)
-        _lib.check(lib.curl_encoder_view_ragged_plan(B, hs.ctypes.data, ws.ctypes.data, cs.ctypes.data, int(bool(has_mask)), size,
-                                                     host.data_ptr(), nbytes), "curl_encoder_view_ragged_plan")
-        if len(_view_ragged_plans) >= _VIEW_RAGGED_PLANS_KEPT:
-            del _view_ragged_plans[next(iter(_view_ragged_plans))]
-        plan = _view_ragged_plans[key] = _ViewRaggedPlan(host, host.to(device))
-    return plan
+    def build():
+        host = _host_plan("curl_encoder_view_ragged_plan", shapes, channels, _lib.VIEW_RAGGED_MAX_IMAGES, (int(bool(has_mask)), size),
+                          lambda hs, ws: (hs, ws, size))
+        return _ViewRaggedPlan(host, host.to(device))
+    return _cached_plan(_view_ragged_plans, _VIEW_RAGGED_PLANS_KEPT, (tuple(shapes), tuple(channels), bool(has_mask), size, device), build)
 
 
 def encoder_view_u8hwc_ragged(images, masks=None, size=_lib.VIEW_SIZE_DEFAULT):
@@ -1669,9 +1623,7 @@ def encoder_view_u8hwc_ragged(images, masks=None, size=_lib.VIEW_SIZE_DEFAULT):
                 None if masks is None else torch.empty(0, 1, size, size, dtype=torch.float32, device=device))
     lib = _lib.load()
     if masks is not None:  # (before anything is packed or uploaded; _ragged_inputs holds the packed arenas to the same)
-        def sizes(x):
-            return [tuple(s) for s in x.shapes] if isinstance(x, RaggedBytes) else [tuple(t.shape) for t in x]
-        want, got = [s[:2] for s in sizes(images)], sizes(masks)
+        want, got = [s[:2] for s in _ragged_sizes(images)], _ragged_sizes(masks)
         if len(got) != len(want):
             raise ValueError(f"masks must hold one mask per image ({len(want)}), got {len(got)}")
         if got != want:
@@ -1686,9 +1638,8 @@ def encoder_view_u8hwc_ragged(images, masks=None, size=_lib.VIEW_SIZE_DEFAULT):
     view = torch.empty(B, 3, size, size, dtype=torch.float32, device=rb.device)
     mview = torch.empty(B, 1, size, size, dtype=torch.float32, device=rb.device) if wm is not None else None
     with torch.cuda.device(rb.device):
-        rc = lib.curl_encoder_view_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), _ptr(wm.arena if wm is not None else None),
-                                                wm.arena.numel() if wm is not None else 0, plan.host.data_ptr(), plan.dev.data_ptr(),
-                                                plan.nbytes, view.data_ptr(), _ptr(mview), size, 0, _stream(rb.arena))
+        rc = lib.curl_encoder_view_ragged_u8hwc(rb.arena.data_ptr(), rb.arena.numel(), *_mask_args(wm), plan.host.data_ptr(),
+                                                plan.dev.data_ptr(), plan.nbytes, view.data_ptr(), _ptr(mview), size, 0, _stream(rb.arena))
     _lib.check(rc, "curl_encoder_view_ragged_u8hwc")
     return view, mview
 
